@@ -3,14 +3,14 @@
 A step = one udpdk_gpu_rx call over one batch of frames already resident in HBM (single-lane
 batches: rx_classify + rx_compact1; otherwise rx_classify + rx_scan + rx_scatter). The timed
 region is exactly K steps between a barrier + hipDeviceSynchronize on each side (host wall
-clock: `value`); an untimed pass of K steps before it gives the GPU time (two events on the
-library stream) and the per-kernel durations (events carried by the kernel dispatches
-themselves, hipExtLaunchKernelGGL, so they agree with rocprofv3's kernel trace).
+clock: `value`); with --full an untimed pass of K steps before it gives the GPU time (two
+events on the library stream) and the per-kernel durations (events carried by the kernel
+dispatches themselves, hipExtLaunchKernelGGL, so they agree with rocprofv3's kernel trace).
 
 Workload: BASELINE.json configs[1] at every N (1 M synthetic 64 B Eth/IPv4/UDP frames, 1 bound
 port, per GPU: weak scaling, no data-path collective), so the driver's per-N values compare one
-workload. Beside it, at every N, the `scale` object measures the scaling workload BASELINE.json
-configs[4] (config 5) the same way: every rank processes its own independent 4 M x 64 B shard
+workload. Beside it (--full), at every N, the `scale` object measures the scaling workload
+BASELINE.json configs[4] (config 5) the same way: every rank processes its own independent 4 M x 64 B shard
 over 4096 ports, Zipf-0.99 (ports seeded 1000 + rank, frames 0x5EED ^ rank), barrier + max over
 ranks, aggregate over all GPUs. Each rank reports its GPU's PCI bus id; with N > 1 they must be
 distinct (UDPDK_BENCH_SHARED_DEVICE=1 allows a rehearsal with every rank on one GPU).
@@ -22,6 +22,12 @@ directly with N > 1, bench.py spawns N worker processes itself (one per GPU, glo
 To keep the 256 MiB Infinity Cache from serving the 64 B batch (≈80 MB) out of cache, the timed
 loop rotates over enough device copies of the batch that a copy is evicted before its reuse
 (> 512 MiB in flight), so every step reads its frames from HBM.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline value needs:
+set-up, W warm-up steps, the K timed steps, the result line. Every other measurement (GPU-event
+and per-kernel times, the roofline, `scale`, `strong`, the CPU baseline, the side lines) runs
+only with `--full`, where the --no-* switches still drop single parts. `--dump-outputs DIR`
+writes the outputs of the last timed step (verdict words and lanes) as DIR/<name>.npy.
 
 Prints ONE JSON line on rank 0.
 """
@@ -51,6 +57,11 @@ def parse():
                    help="GPUs (one process each); default WORLD_SIZE, else 1")
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline value: GPU-event and per-kernel "
+                        "times, roofline, `scale`, `strong`, CPU baseline, side lines")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
     p.add_argument("--config", type=int, default=None,
                    help="BASELINE.json config number (1..5) of the headline line; default 2")
     p.add_argument("--no-scale", action="store_true", help="skip the config-5 `scale` object")
@@ -128,7 +139,8 @@ class Rx:
         self.third = "rx_compact1" if w.n_sockets <= 1 else "rx_scatter"
 
     def step(self, i: int):
-        a = self.args[i % self.copies]
+        self.last = i % self.copies
+        a = self.args[self.last]
         rc = self.f(self.h, a[0], a[1])
         if rc:
             raise abi.UdpdkError(f"udpdk_gpu_rx rc={rc}")
@@ -198,8 +210,9 @@ def device_sync():
         raise RuntimeError(f"hipDeviceSynchronize failed: {rc}")
 
 
-def time_loop(rx: Rx, steps: int, warmup: int, barrier, timing_every: int):
-    """`warmup` untimed calls; then, also untimed, the `steps` calls once between two events on
+def time_loop(rx: Rx, steps: int, warmup: int, barrier, timing_every: int, events: bool = True):
+    """`warmup` untimed calls; then (unless events=False: the timed region alone, GPU time and
+    kernel times not measured), also untimed, the `steps` calls once between two events on
     the library stream (GPU time, with a join so that the other pipes' calls are inside) and with
     the library's per-kernel timing mode (events riding on the kernel dispatches themselves, on
     every `timing_every`-th call). Then the timed region (value): the same number of calls
@@ -209,22 +222,24 @@ def time_loop(rx: Rx, steps: int, warmup: int, barrier, timing_every: int):
     for i in range(warmup):
         rx.step(i)
     rx.check()
-    ev = HipEvents(ctx)
-    ctx.timing(timing_every)
-    ctx.timing_read()                    # reset accumulators
-    ctx.sync()
-    ev.record(0)
-    for i in range(steps):
-        rx.step(warmup + i)
-    ctx.join()                           # the other pipes' calls before the closing event
-    ev.record(1)
-    ctx.sync()
-    gpu_ms = ev.elapsed_ms()
-    ev.close()
-    ms, n = ctx.timing_read() if timing_every else ([0.0] * abi.N_KERNEL_IDS, [0] * abi.N_KERNEL_IDS)
-    ctx.timing(0)
-    kt = {name: 1e3 * ms[k] / n[k] for k, name in
-          enumerate(("rx_classify", "rx_scan", rx.third)) if n[k]}
+    gpu_ms, kt = 0.0, {}
+    if events:
+        ev = HipEvents(ctx)
+        ctx.timing(timing_every)
+        ctx.timing_read()                    # reset accumulators
+        ctx.sync()
+        ev.record(0)
+        for i in range(steps):
+            rx.step(warmup + i)
+        ctx.join()                           # the other pipes' calls before the closing event
+        ev.record(1)
+        ctx.sync()
+        gpu_ms = ev.elapsed_ms()
+        ev.close()
+        ms, n = ctx.timing_read() if timing_every else ([0.0] * abi.N_KERNEL_IDS, [0] * abi.N_KERNEL_IDS)
+        ctx.timing(0)
+        kt = {name: 1e3 * ms[k] / n[k] for k, name in
+              enumerate(("rx_classify", "rx_scan", rx.third)) if n[k]}
     # the timed region
     barrier()
     device_sync()
@@ -236,6 +251,31 @@ def time_loop(rx: Rx, steps: int, warmup: int, barrier, timing_every: int):
     barrier()
     st = rx.check()
     return (t1 - t0), gpu_ms / steps, kt, st
+
+
+DUMP_BUDGET = 64 << 20   # bytes of .npy payload --dump-outputs may write in all
+
+
+def dump_outputs(ctx, rx: Rx, out_dir: str) -> dict:
+    """What the caller of the last timed udpdk_gpu_rx call received, as out_dir/<name>.npy: the
+    verdict words (`meta`, one per frame), the lane offsets (`lane_off`, lanes + 1) and the lane
+    entries (`lane_pkt`, lane_off[-1] frame indices), each u32 value stored exactly as float64.
+    An array too long for its share of DUMP_BUDGET is cut to a fixed sample: the elements at
+    sorted indices drawn from a seeded generator, the same from run to run."""
+    out = rx.args[rx.last][5]
+    meta = ctx.download(out.meta, np.uint32, rx.n)
+    loff = ctx.download(out.lane_off, np.uint32, rx.w.n_sockets + 1)
+    pkt = ctx.download(out.lane_pkt, np.uint32, int(loff[-1]))
+    cap = (DUMP_BUDGET // 8 - loff.size) // 2
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, a in (("meta", meta), ("lane_off", loff), ("lane_pkt", pkt)):
+        sampled = a.size > cap
+        if sampled:
+            a = a[np.sort(np.random.default_rng(0xD0).integers(0, a.size, cap))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+        info[name] = {"elements": int(a.size), "sampled": sampled}
+    return info
 
 
 def _digest(*arrays) -> str:
@@ -920,6 +960,44 @@ def scale_line(ctx, world: int, rank: int, barrier, dist, steps: int, warmup: in
     return out
 
 
+def roofline(w, cls_bytes: int, cls_us: float) -> dict:
+    """The `roofline` object: rx_classify's algorithmic bytes per launch over its duration against
+    the HBM peak, beside the measured traffic and the rocprofv3 kernel time recorded under
+    profiles/ for this workload (where there are any)."""
+    achieved = cls_bytes / (cls_us / 1e6) / 1e9
+
+    traffic = None
+    tf = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tf):
+        try:
+            with open(tf) as f:
+                traffic = json.load(f)["workloads"].get(w.name, {}).get("rx_classify_hbm_bytes_per_launch")
+        except Exception:
+            traffic = None
+
+    rocprof = None
+    rf = os.path.join(ROOT, "profiles", "rocprof_classify.json")
+    if os.path.exists(rf):
+        try:
+            with open(rf) as f:
+                r = json.load(f)["workloads"].get(w.name)
+            if r:
+                rocprof = {"kernel_us": r["mean_us"], "source": r["source"],
+                           "achieved": round(cls_bytes / r["mean_us"] / 1e3, 1),
+                           "frac": round(cls_bytes / r["mean_us"] / 1e3 / HBM_PEAK_GBS, 4)}
+        except Exception:
+            rocprof = None
+
+    return {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic, "kernel": "rx_classify",
+            "traffic_source": "profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                              "passes of this workload (tools/pmc_traffic.sh)",
+            "algorithmic_bytes_per_launch": cls_bytes,
+            "kernel_us_events": round(cls_us, 3),
+            "rocprof": rocprof}
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -945,7 +1023,6 @@ def main():
         finally:
             os.dup2(saved, 1)
             os.close(saved)
-    import torch
     if args.dry_run:
         return dry_run(args, world, rank, dist)
 
@@ -961,7 +1038,8 @@ def main():
     if args.strong_total:
         frames = -(-args.strong_total // world)          # this rank's contiguous shard
     w = F.config_batch(args.config, n=frames, shard=rank)
-    strong_n = 0 if (args.no_strong or args.strong_total) else \
+    full = args.full
+    strong_n = 0 if (not full or args.no_strong or args.strong_total) else \
         len(strong_pieces(world, rank, args.strong_pieces)) * args.strong_piece
     ctx = abi.GpuContext(device, max_frames=max(w.batch.n, 1 << 22, strong_n), max_lanes=4096)
     rx = Rx(ctx, w, args.rotate_mib << 20)
@@ -969,31 +1047,37 @@ def main():
     if args.pipeline is None:
         args.pipeline = auto_depth(w)
     ctx.pipeline(args.pipeline)
-    wall, gpu_step, _, st = time_loop(rx, args.steps, args.warmup, barrier, 0)
-    # kernel durations for the roofline: the same calls one at a time (depth 1), every
-    # --timing-every-th call carrying dispatch events, so each kernel runs without a neighbour
-    ctx.pipeline(1)
-    k_steps = max(16, args.steps // 2)
-    wall1, gpu_step1, kt, _ = time_loop(rx, k_steps, 5, barrier, args.timing_every)
-    # one isolated call (a single launch beside the steady state): events around
-    # one udpdk_gpu_rx on an idle GPU, on a device copy not touched by the previous calls
-    ev1 = HipEvents(ctx)
-    ctx.sync()
-    ev1.record(0)
-    rx.step(k_steps + 5 + rx.copies // 2)
-    ev1.record(1)
-    ctx.sync()
-    single_us = 1e3 * ev1.elapsed_ms()
-    ev1.close()
-    cls_bytes = rx.classify_bytes()
+    wall, gpu_step, _, st = time_loop(rx, args.steps, args.warmup, barrier, 0, events=full)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(ctx, rx, args.dump_outputs)
     mine = {"rank": rank, "device": device, "pci_bus_id": pci_bus_id(device), "frames": rx.n,
             "mpkt_s": round(rx.n * args.steps / wall / 1e6, 2),
-            "gbps": round(rx.pipeline_bytes() * args.steps / wall / 1e9, 1),
+            "gbps": round(rx.pipeline_bytes() * args.steps / wall / 1e9, 1)}
+    if full:
+        # kernel durations for the roofline: the same calls one at a time (depth 1), every
+        # --timing-every-th call carrying dispatch events, so each kernel runs without a neighbour
+        ctx.pipeline(1)
+        k_steps = max(16, args.steps // 2)
+        wall1, gpu_step1, kt, _ = time_loop(rx, k_steps, 5, barrier, args.timing_every)
+        # one isolated call (a single launch beside the steady state): events
+        # around one udpdk_gpu_rx on an idle GPU, on a device copy not touched by the previous calls
+        ev1 = HipEvents(ctx)
+        ctx.sync()
+        ev1.record(0)
+        rx.step(k_steps + 5 + rx.copies // 2)
+        ev1.record(1)
+        ctx.sync()
+        single_us = 1e3 * ev1.elapsed_ms()
+        ev1.close()
+        cls_bytes = rx.classify_bytes()
+        mine.update({
             "classify_us": round(kt.get("rx_classify", 0.0), 3),
             "classify_gbps": round(cls_bytes / kt["rx_classify"] / 1e3, 1) if kt.get("rx_classify") else None,
-            "kernel_us": {k: round(v, 3) for k, v in kt.items()}}
+            "kernel_us": {k: round(v, 3) for k, v in kt.items()}})
     per_rank = [mine]
     if dist is not None:
+        import torch
         t = torch.tensor([wall], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
@@ -1004,7 +1088,7 @@ def main():
         raise SystemExit(f"ranks share a GPU: {[p['pci_bus_id'] for p in per_rank]} "
                          "(set UDPDK_BENCH_SHARED_DEVICE=1 for a one-GPU rehearsal)")
     scale = None
-    if not args.no_scale and not args.strong_total:
+    if full and not args.no_scale and not args.strong_total:
         scale = scale_line(ctx, world, rank, barrier, dist, max(20, args.steps // 4), 5,
                            args.rotate_mib << 20)
         scale["distinct_gpus"] = distinct
@@ -1015,30 +1099,6 @@ def main():
     total_pkts = rx.n * args.steps * world
     mpkt_s = total_pkts / wall / 1e6
     ms_step = 1e3 * wall / args.steps
-    cls_us = kt.get("rx_classify", 1e3 * gpu_step1)    # timing off: the whole step, an upper bound
-    achieved = cls_bytes / (cls_us / 1e6) / 1e9
-
-    traffic = None
-    tf = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tf):
-        try:
-            with open(tf) as f:
-                traffic = json.load(f)["workloads"].get(w.name, {}).get("rx_classify_hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
-
-    rocprof = None
-    rf = os.path.join(ROOT, "profiles", "rocprof_classify.json")
-    if os.path.exists(rf):
-        try:
-            with open(rf) as f:
-                r = json.load(f)["workloads"].get(w.name)
-            if r:
-                rocprof = {"kernel_us": r["mean_us"], "source": r["source"],
-                           "achieved": round(cls_bytes / r["mean_us"] / 1e3, 1),
-                           "frac": round(cls_bytes / r["mean_us"] / 1e3 / HBM_PEAK_GBS, 4)}
-        except Exception:
-            rocprof = None
 
     line = {
         "metric": "device-resident Mpkt/s + GB/s, RX parse+cksum+port-demux, 64B & 1500B frames",
@@ -1057,29 +1117,28 @@ def main():
                    "frame_bytes_per_gpu": rx.sum_len, "bound_ports": w.n_sockets,
                    "parallelism": f"shard{world}", "device_copies_rotated": rx.copies},
         "gbps_pipeline": round(rx.pipeline_bytes() * args.steps * world / wall / 1e9, 1),
-        "gpu_us_per_step": round(1e3 * gpu_step, 3),
-        "single_call_us": round(single_us, 3),
         "pipeline_depth": args.pipeline,
-        "depth1": {"mpkt_s": round(rx.n * k_steps / wall1 / 1e6, 2), "gpu_us_per_step": round(1e3 * gpu_step1, 3),
-                   "note": "the same calls one at a time on one stream (kernel timing loop)"},
-        "kernel_us": {k: round(v, 3) for k, v in kt.items()},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": traffic, "kernel": "rx_classify",
-                     "traffic_source": "profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                       "passes of this workload (tools/pmc_traffic.sh)",
-                     "algorithmic_bytes_per_launch": cls_bytes,
-                     "kernel_us_events": round(cls_us, 3),
-                     "rocprof": rocprof},
+        "full": full,
         "cpu_baseline": None,
     }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
+    if full:
+        line.update({
+            "gpu_us_per_step": round(1e3 * gpu_step, 3),
+            "single_call_us": round(single_us, 3),
+            "depth1": {"mpkt_s": round(rx.n * k_steps / wall1 / 1e6, 2), "gpu_us_per_step": round(1e3 * gpu_step1, 3),
+                       "note": "the same calls one at a time on one stream (kernel timing loop)"},
+            "kernel_us": {k: round(v, 3) for k, v in kt.items()},
+            # timing off: the whole step stands for rx_classify, an upper bound
+            "roofline": roofline(w, cls_bytes, kt.get("rx_classify", 1e3 * gpu_step1))})
     line["per_rank"] = per_rank
     line["distinct_gpus"] = distinct
     if scale is not None:
         line["scale"] = scale
     if strong is not None:
         line["strong"] = strong
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         gdig = gpu_digest(ctx, rx.args[0][5], rx.n, w.n_sockets) if rx.n <= (1 << 22) else None
         res, cores = cpu_baseline(w, args.cpu_seconds, gdig)
         best = res["best"]
@@ -1104,7 +1163,7 @@ def main():
             line["config1_cpu"] = config1_line(args.cpu_seconds / 2)
         except Exception as e:
             line["config1_cpu"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_extra:
+    if full and rank == 0 and world == 1 and not args.no_extra:
         extra = []
         for cfg in (1, 3, 4, 5):
             if cfg != args.config:

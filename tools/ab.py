@@ -6,7 +6,7 @@ Variants are built on the CPU side first: `make variant VAR=t4096 VFLAGS="-DUDPD
   python tools/ab.py --libs base,t4096 --bench "--config 5" --reps 2
   python tools/ab.py --libs base,new --line rss --reps 2 --tests tests/test_gpu_rss.py
 
---bench runs bench.py (default extra args: --steps 200 --warmup 20 --no-cpu-baseline --no-extra)
+--bench runs bench.py (default extra args: --full --steps 200 --warmup 20 --no-cpu-baseline --no-extra)
 and prints value / pipelined step / depth-1 step / kernel times per variant and repetition.
 --line runs one of bench.py's side lines in a child process per variant (LINES below).
 --tests first runs those GPU tests once against every non-base variant (parity before timing).
@@ -115,7 +115,7 @@ def main():
                 res = run([sys.executable, os.path.abspath(__file__), "--_line", a.line], env, a.timeout, log)
             else:
                 extra = (a.bench or "").split()
-                dflt = ["--steps", "200", "--warmup", "20", "--no-cpu-baseline", "--no-extra", "--no-strong"]
+                dflt = ["--full", "--steps", "200", "--warmup", "20", "--no-cpu-baseline", "--no-extra", "--no-strong"]
                 res = run([sys.executable, "bench.py", *dflt, *extra], env, a.timeout, log)
             for d in res:
                 print(f"r{rep} {n:10s} {summary(d)}", flush=True)

@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py JSON line (gpurun_out/bench.json by default)."""
+"""One-screen summary of a `bench.py --full` JSON line (the file named by the first argument)."""
 import json
 import sys
 

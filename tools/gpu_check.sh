@@ -16,7 +16,7 @@ run() { # name timeout cmd...
 }
 case ",$STEPS," in *,smoke,*) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()";; esac
 if [ $rc -le 1 ]; then case ",$STEPS," in *,pytest,*) run pytest_gpu 1100 python -m pytest tests -m gpu -x -q ${PYTEST_ARGS};; esac; fi
-if [ $rc -le 1 ]; then case ",$STEPS," in *,bench,*) run bench 600 python bench.py ${BENCH_ARGS};; esac; fi
+if [ $rc -le 1 ]; then case ",$STEPS," in *,bench,*) run bench 600 python bench.py --full ${BENCH_ARGS};; esac; fi
 if [ $rc -le 1 ]; then case ",$STEPS," in *,prof,*)
   export TMPDIR=/tmp
   run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof" -o rx -- python3 "$R/bench.py" --steps 100 --warmup 10 --no-cpu-baseline --no-extra --no-scale --no-strong --pipeline 1
