@@ -39,6 +39,49 @@ constexpr uint32_t SCAN_SMALL_TILES = 32;   // ... and this many tiles (serial p
 
 constexpr int TX_BLOCK = 256;
 
+// Memory policy of rx_classify's streams (chosen by
+// tools/probe/policy_probe.hip and same-box A/Bs): the `aux` cache bits of its gfx950 buffer
+// and global instructions, compile-time constants, per form where the forms disagree (another arm
+// is a library variant: make variant VFLAGS="-DUDPDK_POL_FRAME=2 ..."). AUX_NT marks a stream
+// whose bytes are touched once per call. An nt load also bypasses the CU's L1: the short-frame
+// windows (four loads of a lane into one or two lines) lose a quarter of their speed to it, the
+// long-frame form's chunk and block loads (every line by one load) gain a tenth. AUX_SC1 is the
+// write-through of the fused completion's protocol and is never taken off a store that has it;
+// only AUX_NT may stand beside it ("nt is not write-through", MI355X_MICROARCH.md).
+constexpr int AUX_NT = 2, AUX_SC1 = 16;
+#ifndef UDPDK_POL_FRAME
+#define UDPDK_POL_FRAME 0                    // frame bytes, short-frame one-round form <1, 0>
+#endif
+#ifndef UDPDK_POL_FRAME_LONG
+#define UDPDK_POL_FRAME_LONG AUX_NT          // frame bytes, long-frame form <2, 0> (tail pass, span sweep)
+#endif
+#ifndef UDPDK_POL_FRAME_MR
+#define UDPDK_POL_FRAME_MR 0                 // frame bytes, multi-round forms <G, 1> (multi-lane batches)
+#endif
+#ifndef UDPDK_POL_DESC
+#define UDPDK_POL_DESC AUX_NT                // descriptor staging loads (offset, length, ptype)
+#endif
+#ifndef UDPDK_POL_META
+#define UDPDK_POL_META AUX_NT                // beside sc1 on the fused form's verdict-word stores
+#endif
+#ifndef UDPDK_POL_LANE
+#define UDPDK_POL_LANE AUX_NT                // beside sc1 on the fused form's speculative lane entries
+#endif
+// rx_classify<G, MR, POL>: POL = 1 takes the constants above, POL = 0 the default policy on every
+// stream (UDPDK_RX_POLICY=0 at context creation: tests and A/B run both from one library).
+// Frame-byte loads: the window, the tail pass's chunks, the span sweep's blocks.
+__host__ __device__ constexpr int pol_frame(int G, int MR, int POL)
+{
+    return !POL ? 0 : MR ? UDPDK_POL_FRAME_MR : G == 1 ? UDPDK_POL_FRAME : UDPDK_POL_FRAME_LONG;
+}
+__host__ __device__ constexpr int pol_desc(int POL) { return POL ? UDPDK_POL_DESC : 0; }
+__host__ __device__ constexpr int pol_meta(int POL) { return AUX_SC1 | (POL ? UDPDK_POL_META : 0); }
+__host__ __device__ constexpr int pol_lane(int POL) { return AUX_SC1 | (POL ? UDPDK_POL_LANE : 0); }
+static_assert((UDPDK_POL_FRAME & ~AUX_NT) == 0 && (UDPDK_POL_FRAME_LONG & ~AUX_NT) == 0 &&
+              (UDPDK_POL_FRAME_MR & ~AUX_NT) == 0 && (UDPDK_POL_DESC & ~AUX_NT) == 0 &&
+              (UDPDK_POL_META & ~AUX_NT) == 0 && (UDPDK_POL_LANE & ~AUX_NT) == 0,
+              "a policy constant is 0 or AUX_NT");
+
 // rx_classify LDS carve (one dynamic array, 16-byte aligned offsets: cdna_hip_programming.md
 // Guideline 17): the tail pass's per-wave arrays (chunk starts, frame offsets, datagram ends);
 // per-wave counter rows; the descriptors of one or two rounds of RX_ROUND frames (offset,
@@ -302,8 +345,9 @@ struct GatherArgs {
 };
 
 // G: tail chunk groups in flight (1, 2); MR: tiles of several rounds, whose next round's
-// descriptors are loaded a round ahead (in registers) instead of when they are staged
-template <int G, int MR> __global__ void rx_classify(RxArgs a);
+// descriptors are loaded a round ahead (in registers) instead of when they are staged; POL: the
+// memory policy (1: the policy constants above, 0: default policy everywhere)
+template <int G, int MR, int POL> __global__ void rx_classify(RxArgs a);
 __global__ void rx_gather(GatherArgs a);
 template <uint32_t B> __global__ void rx_scan_cols(ScanArgs a, uint32_t lb);
 __global__ void rx_scan_reduce(ScanArgs a);

@@ -4,7 +4,7 @@
 // burst loop (udpdk_poller.c:516-545) plus the per-socket rx_buffer appends and ring flushes
 // (udpdk_poller.c:274-298). All integer/byte work, bound by HBM:
 //
-//   rx_classify<G, MR>  one workgroup (4 waves) per tile of T frames, lane = frame, each wave
+//   rx_classify<G, MR, POL>  one workgroup (4 waves) per tile of T frames, lane = frame, each wave
 //       walking 64-frame steps in rounds of 1024 frames. The round's descriptors are staged in
 //       LDS; the header window (frame bytes [12, 64), 3 x 16 B + 8 B dword-aligned loads
 //       funnelled to frame-relative words) of the next step is in flight while the current one
@@ -19,7 +19,8 @@
 //       tile's per-lane delivery histogram (tile-major row hist[tile][lane]) and counter row;
 //       single-lane calls also write speculative lane entries and, fused, complete the lane in
 //       the last workgroup (repairing tiles that were not full). MR = 1: multi-round tiles with
-//       the next round's descriptors loaded a round ahead.
+//       the next round's descriptors loaded a round ahead. POL: the cache policy of each stream
+//       (rx_common.h; 0 = default policy everywhere, UDPDK_RX_POLICY=0).
 //   rx_compact1  the single-lane completion as a second launch (fused form not taken): keeps the
 //       speculative entries up to the first tile that was not full, rewrites the rest.
 //   rx_scan_cols + rx_scatterw  general case: per-lane column scan of the tile-major histogram
@@ -116,10 +117,20 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, uint3
                                              0x00020000);
 }
 
+// AUX: the load's cache policy bits (rx_common.h, memory policy)
+template <int AUX>
 __device__ __forceinline__ uint4 load16(__amdgpu_buffer_rsrc_t r, uint32_t off)
 {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, AUX);
     return make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+// a plain pointer load under a policy: AUX_NT = the global load's nt bit
+template <int AUX, typename T>
+__device__ __forceinline__ T load_pol(const T *p)
+{
+    if constexpr ((AUX & AUX_NT) != 0) return __builtin_nontemporal_load(p);
+    else return *p;
 }
 
 // Diagnostic build (-DUDPDK_STAMPS): wave 0 of every workgroup accumulates s_memtime cycles per
@@ -419,7 +430,7 @@ struct Win {
 // batches overlapping on several streams want (config 2, --steps 20, same-box A/B with the
 // compaction launch gone: 57.1 -> 63.0 Gpkt/s; config 1 (106 B, one tail chunk per frame) is
 // 8 % slower at G = 1, so the host picks G by whether recent calls had tail passes).
-template <int G, int MR>
+template <int G, int MR, int POL>
 __global__ void __launch_bounds__(CLS_BLOCK)
 __attribute__((amdgpu_waves_per_eu(MR ? 2 : G == 1 ? 5 : UDPDK_CLS_WPE, 8)))
 rx_classify(RxArgs a)
@@ -427,6 +438,9 @@ rx_classify(RxArgs a)
     static_assert(G == 1 || G == 2, "one or two tail chunk groups in flight");
     // the span sweep (RxArgs::span) is compiled into the long-frame form of one-round tiles only
     constexpr bool SPAN = G == 2 && MR == 0;
+    // this form's memory policy: frame-byte loads, descriptor loads, the fused form's stores
+    constexpr int PF = pol_frame(G, MR, POL), PD = pol_desc(POL);
+    constexpr int PM = pol_meta(POL), PL = pol_lane(POL);
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
     const uint32_t steps = a.tile_frames / 64;
@@ -493,9 +507,9 @@ rx_classify(RxArgs a)
 #pragma unroll
         for (uint32_t i = 0; i < SPT; ++i) {
             const uint32_t pc = min(t0 + r * RX_ROUND + i * CLS_BLOCK + tid, plast);
-            o[i] = a.offset[pc];
-            l[i] = a.length[pc];
-            t[i] = ptw[pc];
+            o[i] = load_pol<PD>(a.offset + pc);
+            l[i] = load_pol<PD>(a.length + pc);
+            t[i] = load_pol<PD>(ptw + pc);
         }
     };
     auto stage_store = [&](uint32_t r, const uint32_t (&o)[SPT], const uint32_t (&l)[SPT], const uint32_t (&t)[SPT]) {
@@ -531,10 +545,10 @@ rx_classify(RxArgs a)
         const bool ok = s < steps && p < t1 && l >= 14u && l <= a.frames_bytes && o <= a.frames_bytes - l;
         const uint32_t b = swept ? OOR : ok ? (o + 12u) & ~3u : 0u;
         Win r;
-        r.a = load16(fr, b);
-        r.b = load16(fr, b + 16u);
-        r.c = load16(fr, b + 32u);
-        const auto d = __builtin_amdgcn_raw_buffer_load_b64(fr, (int)(b + 48u), 0, 0);
+        r.a = load16<PF>(fr, b);
+        r.b = load16<PF>(fr, b + 16u);
+        r.c = load16<PF>(fr, b + 32u);
+        const auto d = __builtin_amdgcn_raw_buffer_load_b64(fr, (int)(b + 48u), 0, PF);
         r.d = make_uint2(d[0], d[1]);
         return r;
     };
@@ -658,7 +672,7 @@ rx_classify(RxArgs a)
                 lead_b = mark != 0u ? bq & 3u : 0u;     // a frame's first chunk: its lead bytes
                 const uint32_t base = (bq & ~3u) + 64u * k;
 #pragma unroll
-                for (int c = 0; c < 4; ++c) R[c] = load16(fr, 16 * c < left ? base + 16u * c : OOR);
+                for (int c = 0; c < 4; ++c) R[c] = load16<PF>(fr, 16 * c < left ? base + 16u * c : OOR);
             };
             // The full-chunk sum reads every loaded register unconditionally, so the compiler's
             // wait for this group is placed here on every path.
@@ -791,7 +805,7 @@ rx_classify(RxArgs a)
 #pragma unroll
             for (uint32_t c = 0; c < 4; ++c) {
                 const uint32_t x = A + 4096u * g + 1024u * c + 16u * lane;
-                R[c] = load16(fr, x < Ep ? x : OOR);
+                R[c] = load16<PF>(fr, x < Ep ? x : OOR);
             }
         };
         auto consume = [&](uint32_t g, const uint4 (&R)[4]) {
@@ -1169,12 +1183,12 @@ rx_classify(RxArgs a)
                 make_rsrc(a.spec_pkt, a.spec_cap >= 0x40000000u ? 0xFFFFFFFCu : a.spec_cap * 4u);
             if (d == 0xFu && (pos & 3u) == 0u) {
                 const __attribute__((ext_vector_type(4))) uint32_t x = {f, f + 1u, f + 2u, f + 3u};
-                __builtin_amdgcn_raw_buffer_store_b128(x, sr, (int)(4u * pos), 0, 16);
+                __builtin_amdgcn_raw_buffer_store_b128(x, sr, (int)(4u * pos), 0, PL);
             } else {
 #pragma unroll
                 for (uint32_t j = 0; j < 4; ++j)
                     if ((d >> j) & 1u) {
-                        __builtin_amdgcn_raw_buffer_store_b32(f + j, sr, (int)(4u * pos), 0, 16);
+                        __builtin_amdgcn_raw_buffer_store_b32(f + j, sr, (int)(4u * pos), 0, PL);
                         ++pos;
                     }
             }
@@ -1202,14 +1216,14 @@ rx_classify(RxArgs a)
                     const uint4 v = s4[i];
                     const __attribute__((ext_vector_type(4))) uint32_t x = {v.x, v.y, v.z, v.w};
                     if (4u * i + 4u <= nv)
-                        __builtin_amdgcn_raw_buffer_store_b128(x, mr, (int)(16u * i), 0, 16);
+                        __builtin_amdgcn_raw_buffer_store_b128(x, mr, (int)(16u * i), 0, PM);
                     else
                         for (uint32_t j = 4u * i; j < nv; ++j)
-                            __builtin_amdgcn_raw_buffer_store_b32(mstage[j], mr, (int)(4u * j), 0, 16);
+                            __builtin_amdgcn_raw_buffer_store_b32(mstage[j], mr, (int)(4u * j), 0, PM);
                 }
             } else {
                 for (uint32_t i = tid; i < nv; i += CLS_BLOCK)
-                    __builtin_amdgcn_raw_buffer_store_b32(mstage[i], mr, (int)(4u * i), 0, 16);
+                    __builtin_amdgcn_raw_buffer_store_b32(mstage[i], mr, (int)(4u * i), 0, PM);
             }
         } else if (nv == a.tile_frames && ((uintptr_t)dst & 15u) == 0) {
             uint4 *d4 = reinterpret_cast<uint4 *>(dst);
@@ -1284,10 +1298,14 @@ rx_classify(RxArgs a)
     if (a.dbg && w == 0 && lane < 16) a.dbg[blockIdx.x * 16 + lane] = st_acc[lane];
 #endif
 }
-template __global__ void rx_classify<1, 0>(RxArgs a);
-template __global__ void rx_classify<2, 0>(RxArgs a);
-template __global__ void rx_classify<1, 1>(RxArgs a);
-template __global__ void rx_classify<2, 1>(RxArgs a);
+template __global__ void rx_classify<1, 0, 0>(RxArgs a);
+template __global__ void rx_classify<2, 0, 0>(RxArgs a);
+template __global__ void rx_classify<1, 1, 0>(RxArgs a);
+template __global__ void rx_classify<2, 1, 0>(RxArgs a);
+template __global__ void rx_classify<1, 0, 1>(RxArgs a);
+template __global__ void rx_classify<2, 0, 1>(RxArgs a);
+template __global__ void rx_classify<1, 1, 1>(RxArgs a);
+template __global__ void rx_classify<2, 1, 1>(RxArgs a);
 
 
 // ------------------------------------------------------------------------------------------

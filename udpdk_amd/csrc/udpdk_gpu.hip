@@ -116,6 +116,7 @@ struct udpdk_gpu_ctx {
     int force_tailg = 0;           // UDPDK_RX_TAILG=1/2 (tests, A/B): rx_classify<G> always
     int force_mr = -1;             // UDPDK_RX_MR=0/1 (tests, A/B): the round-ahead descriptor form
     bool no_span = false;          // UDPDK_RX_SPAN=0 (tests, A/B): no span sweep (RxArgs::span)
+    int policy = 1;                // UDPDK_RX_POLICY=0 (tests, A/B): rx_classify<.., 0>, default memory policy
     bool trace = false;            // UDPDK_RX_TRACE (diagnostic): the form of every call on stderr
     bool no_inline = false;        // UDPDK_RX_NO_INLINE (tests, A/B): always the port-table loads
     uint32_t scatter_group_frames = UDPDK_SCATTER_GROUP_FRAMES;   // UDPDK_SCATTER_GROUP_FRAMES (tests, A/B)
@@ -202,6 +203,16 @@ int fold_timing(udpdk_gpu_ctx *c)
     }
     c->n_sets_used = 0;
     return 0;
+}
+
+// rx_classify<g, mr, pol>: g tail chunk groups in flight (1, 2), round-ahead descriptors, memory policy
+using ClassifyKernel = void (*)(RxArgs);
+ClassifyKernel classify_form(int g, int mr, int pol)
+{
+    static const ClassifyKernel form[2][2][2] = {
+        {{rx_classify<1, 0, 0>, rx_classify<1, 0, 1>}, {rx_classify<1, 1, 0>, rx_classify<1, 1, 1>}},
+        {{rx_classify<2, 0, 0>, rx_classify<2, 0, 1>}, {rx_classify<2, 1, 0>, rx_classify<2, 1, 1>}}};
+    return form[g - 1][mr][pol];
 }
 
 // Launch on the context stream; with a timing set, kernel k's dispatch carries the set's start
@@ -310,6 +321,7 @@ int udpdk_gpu_ctx_create(int device, uint32_t max_frames, uint32_t max_lanes, ud
     c->no_inline = getenv("UDPDK_RX_NO_INLINE") != nullptr;
     if (const char *e = getenv("UDPDK_RX_MR")) c->force_mr = atoi(e) ? 1 : 0;
     if (const char *e = getenv("UDPDK_RX_SPAN")) c->no_span = atoi(e) == 0;
+    if (const char *e = getenv("UDPDK_RX_POLICY")) c->policy = atoi(e) ? 1 : 0;
     if (const char *e = getenv("UDPDK_SCATTER_GROUP_FRAMES")) c->scatter_group_frames = (uint32_t)atoi(e);
     if (const char *e = getenv("UDPDK_SCATTER_MIN_WG")) c->scatter_min_wg = (uint32_t)atoi(e);
     if (const char *e = getenv("UDPDK_RX_TAILG")) {
@@ -365,14 +377,11 @@ int udpdk_gpu_ctx_create(int device, uint32_t max_frames, uint32_t max_lanes, ud
             std::max(classify_lds_bytes(UDPDK_GPU_MAX_LANES, RX_TILE_MAX),
                      classify_lds_bytes(UDPDK_GPU_MAX_LANES, RX_ROUND) + SPAN_LDS_BYTES),
             160u * 1024u - 1024u);   // static LDS besides
-        if (hipFuncSetAttribute((const void *)rx_classify<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                cls_lds) != hipSuccess) break;
-        if (hipFuncSetAttribute((const void *)rx_classify<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                cls_lds) != hipSuccess) break;
-        if (hipFuncSetAttribute((const void *)rx_classify<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                cls_lds) != hipSuccess) break;
-        if (hipFuncSetAttribute((const void *)rx_classify<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                cls_lds) != hipSuccess) break;
+        for (int g = 1; g <= 2 && ok; ++g)
+            for (int mr = 0; mr <= 1 && ok; ++mr)
+                ok = hipFuncSetAttribute((const void *)classify_form(g, mr, c->policy),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, cls_lds) == hipSuccess;
+        if (!ok) break;
         if (hipFuncSetAttribute((const void *)rx_scatter, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)scatter1_lds_bytes(UDPDK_GPU_MAX_LANES)) != hipSuccess) break;
         if (hipFuncSetAttribute((const void *)rx_scatterw<SCATTER_WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -723,7 +732,7 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
     // tiles of several rounds (many lanes: config 5's 8192-frame tiles) take the form that loads
     // each next round's descriptors a round ahead
     const bool mr = c->force_mr >= 0 ? c->force_mr == 1 : T > (uint32_t)RX_ROUND;
-    auto cls = tailg == 1 ? (mr ? rx_classify<1, 1> : rx_classify<1, 0>) : (mr ? rx_classify<2, 1> : rx_classify<2, 0>);
+    auto cls = classify_form(tailg, mr ? 1 : 0, c->policy);
     // the span sweep: the long-frame form of one-round tiles (its LDS ring after the carve)
     const uint32_t cls_lds = classify_lds_bytes(S, T, hist16);
     ra.span = tailg == 2 && !mr && T == (uint32_t)RX_ROUND && !c->no_span &&
