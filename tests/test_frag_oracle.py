@@ -58,6 +58,54 @@ def test_fragment_round_trip(L, mtu):
     assert bytes(ip_payload) == fr[34:]                         # UDP header + payload
 
 
+# the lengths tests/test_gpu_tx_edges.py compares the GPU with the oracle at, per MTU
+MTU_EDGES = {68: list(range(121)) + [1000],
+             572: [529, 530, 531, 544, 545, 1096, 1097],
+             65532: [65490, 65491, 65507]}
+
+
+@pytest.mark.parametrize("mtu", sorted(MTU_EDGES))
+def test_fragment_mtu_edges(mtu):
+    """The ends of the MTU range (68, 65532) and a small one between, rebuilt from the inputs with
+    no oracle in between: the fragments' IPv4 payloads concatenate to the UDP header + payload,
+    every fragment header sums to 0xFFFF (RFC 1071), MF is set on all but the last, the fragment
+    offsets are contiguous, and fragment k starts k * (mtu + 14) bytes into the span."""
+    fpl = mtu - 20
+    for L in MTU_EDGES[mtu]:
+        fr, pay = _frame(L, L)
+        frags = O.tx_fragment(fr, mtu)
+        blob = b"".join(frags)
+        assert len(blob) == abi.lib().udpdk_gpu_tx_span(L, mtu, None)
+        if L + 42 <= mtu:
+            assert blob == fr and fr[42:] == pay
+            continue
+        ipp = fr[34:42] + pay
+        assert fr[38:40] == (L + 8).to_bytes(2, "big") and fr[40:42] == b"\0\0"
+        nf = -(-len(ipp) // fpl)
+        assert len(frags) == nf
+        off = 0
+        for k in range(nf):
+            m = min(fpl, len(ipp) - off)
+            f = blob[k * (mtu + 14):k * (mtu + 14) + 34 + m]
+            assert f == frags[k]
+            h = f[14:34]
+            assert _sum16(h) == 0xFFFF
+            assert (h[2] << 8 | h[3]) == 20 + m
+            ff = h[6] << 8 | h[7]
+            assert (ff & 0x1FFF) * 8 == off and bool(ff & 0x2000) == (k + 1 < nf) and not ff & 0xC000
+            assert f[34:] == ipp[off:off + m]
+            off += m
+        assert off == len(ipp)
+
+
+def test_mtu_576_is_no_mtu_of_the_abi():
+    """576 - 20 is no multiple of 8 (fragment offsets count 8-byte units): the span helper treats
+    it like every MTU udpdk_gpu_tx_build_mtu rejects, one unfragmented frame."""
+    n = abi.C.c_uint32()
+    for L in (533, 534, 535, 548, 549, 1104, 1105):
+        assert abi.lib().udpdk_gpu_tx_span(L, 576, abi.C.byref(n)) == L + 42 and n.value == 1
+
+
 def test_fragment_known_answer_2006():
     """Independent restatement of one case: the largest sendto that fits a 2048 B mbuf
     (RTE_MBUF_DEFAULT_BUF_SIZE data room, udpdk_init.c:78-99) at IPV4_MTU_DEFAULT."""

@@ -121,6 +121,9 @@ struct udpdk_gpu_ctx {
     bool no_inline = false;        // UDPDK_RX_NO_INLINE (tests, A/B): always the port-table loads
     uint32_t scatter_group_frames = UDPDK_SCATTER_GROUP_FRAMES;   // UDPDK_SCATTER_GROUP_FRAMES (tests, A/B)
     uint32_t scatter_min_wg = UDPDK_SCATTER_MIN_WG;               // UDPDK_SCATTER_MIN_WG (tests, A/B)
+    uint32_t tx_parts = 0;         // UDPDK_TX_PARTS=1..4 (tests): TxArgs::parts, 0 = computed per batch
+    uint32_t tx_grid = 4096;       // UDPDK_TX_GRID>=1 (tests): tx_build's workgroup cap
+    uint32_t gather_grid = 16384;  // UDPDK_GATHER_GRID>=1 (tests): rx_gather's workgroup cap
     bool have_snapshot = false;
 
     // RX workspace, one set per pipe
@@ -328,6 +331,10 @@ int udpdk_gpu_ctx_create(int device, uint32_t max_frames, uint32_t max_lanes, ud
         const int g = atoi(e);
         if (g == 1 || g == 2) c->force_tailg = g;
     }
+    // (out-of-range values are clamped)
+    if (const char *e = getenv("UDPDK_TX_PARTS")) c->tx_parts = (uint32_t)std::min(std::max(atoi(e), 1), 4);
+    if (const char *e = getenv("UDPDK_TX_GRID")) c->tx_grid = (uint32_t)std::max(atoi(e), 1);
+    if (const char *e = getenv("UDPDK_GATHER_GRID")) c->gather_grid = (uint32_t)std::max(atoi(e), 1);
     int rc = -EIO;
     do {
         if (hipSetDevice(device) != hipSuccess) break;
@@ -1113,7 +1120,7 @@ static int rx_gather_launch(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const 
     ga.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
     ga.n = bt->n;
     ga.slot_off = slot_off_dev;
-    const uint32_t grid = std::min<uint32_t>(ceil_div(count, GATHER_BLOCK), 16384);
+    const uint32_t grid = std::min<uint32_t>(ceil_div(count, GATHER_BLOCK), c->gather_grid);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->timing_every) {
         HIPC(c, hipEventCreate(&e0));
@@ -1453,7 +1460,8 @@ int udpdk_gpu_tx_build_mtu(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
     // waves per group of 64 datagrams: up to 4 while groups alone would leave the chip under
     // ~16 K waves (their chunk sweeps split between them)
     ta.parts = std::max<uint32_t>(1u, std::min<uint32_t>(4u, 16384u / std::max<uint32_t>(groups, 1u)));
-    const uint32_t grid = std::min<uint32_t>(ceil_div(groups * ta.parts, TX_BLOCK / 64), 4096);
+    if (c->tx_parts) ta.parts = c->tx_parts;
+    const uint32_t grid = std::min<uint32_t>(ceil_div(groups * ta.parts, TX_BLOCK / 64), c->tx_grid);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->timing_every) {
         HIPC(c, hipEventCreate(&e0));
