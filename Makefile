@@ -9,13 +9,13 @@ INC       := -Iinclude -Iudpdk_amd/csrc
 LIB       := udpdk_amd/libudpdk_amd.so
 OBJDIR    := build/obj
 
-HIP_SRC   := udpdk_amd/csrc/rx_kernels.hip udpdk_amd/csrc/rx_gather.hip udpdk_amd/csrc/rx_reasm.hip udpdk_amd/csrc/rx_rss.hip udpdk_amd/csrc/tx_kernels.hip \
-             udpdk_amd/csrc/udpdk_gpu.hip
+HIP_SRC   := udpdk_amd/csrc/rx_classify.hip udpdk_amd/csrc/rx_lanes.hip udpdk_amd/csrc/rx_gather.hip udpdk_amd/csrc/rx_reasm.hip \
+             udpdk_amd/csrc/rx_rss.hip udpdk_amd/csrc/tx_kernels.hip udpdk_amd/csrc/udpdk_gpu.hip
 C_SRC     := $(wildcard udpdk_amd/csrc/host/*.c)
 HIP_OBJ   := $(patsubst udpdk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
 C_OBJ     := $(patsubst udpdk_amd/csrc/host/%.c,$(OBJDIR)/host/%.o,$(C_SRC))
 HDRS      := include/udpdk_gpu.h include/udpdk_api.h udpdk_amd/csrc/rx_common.h \
-             $(wildcard udpdk_amd/csrc/host/*.h)
+             udpdk_amd/csrc/wave.h udpdk_amd/csrc/stamps.h $(wildcard udpdk_amd/csrc/host/*.h)
 
 TOOLS     := tools/bin/bench_sock
 
@@ -82,10 +82,14 @@ tools/var/$(VAR).so: $(VAR_OBJ)
 	    -Wl,-soname,libudpdk_amd.so -Wl,--version-script=udpdk_amd/csrc/libudpdk_amd.map
 FORCE:
 
-asm: udpdk_amd/csrc/rx_kernels.hip $(HDRS)
+# device assembly and the resource-usage report of every HIP source: build/asm/<file>.s,
+# build/asm/<file>_resource.txt (tools/diag/asm_stats.py reads the .s)
+ASM_OUT   := $(patsubst udpdk_amd/csrc/%.hip,build/asm/%.s,$(HIP_SRC))
+asm: $(ASM_OUT)
+build/asm/%.s: udpdk_amd/csrc/%.hip $(HDRS)
 	@mkdir -p build/asm
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument $(INC) -S --cuda-device-only -o build/asm/rx_kernels.s $<
-	$(HIPCC) $(HIPFLAGS) $(INC) -c -Rpass-analysis=kernel-resource-usage $< -o /dev/null 2> build/asm/rx_resource.txt || true
+	$(HIPCC) $(HIPFLAGS) -Wno-unused-command-line-argument $(INC) -S --cuda-device-only -o $@ $<
+	$(HIPCC) $(HIPFLAGS) $(INC) -c -Rpass-analysis=kernel-resource-usage $< -o /dev/null 2> build/asm/$*_resource.txt || true
 
 clean:
 	rm -rf build $(LIB) $(TOOLS)

@@ -1,11 +1,15 @@
-"""Instruction mix per loop depth of a kernel in build/asm/rx_kernels.s (make asm), using the
-compiler's own "Loop: Header=... Depth=N" block annotations."""
+"""Instruction mix per loop depth of a kernel in a device assembly file of `make asm`
+(build/asm/<file>.s), using the compiler's own "Loop: Header=... Depth=N" block annotations.
+
+    python tools/diag/asm_stats.py [file.s [mangled kernel name]]
+"""
 import collections
 import re
 import sys
 
-kern = sys.argv[1] if len(sys.argv) > 1 else "_ZN5udpdk11rx_classifyILb1EEEvNS_6RxArgsE"
-s = open("build/asm/rx_kernels.s").read()
+path = sys.argv[1] if len(sys.argv) > 1 else "build/asm/rx_classify.s"
+kern = sys.argv[2] if len(sys.argv) > 2 else "_ZN5udpdk11rx_classifyILi1ELi0ELi1EEEvNS_6RxArgsE"
+s = open(path).read()
 start = s.index(kern + ":")
 end = s.index(".Lfunc_end", start)
 depth, header = 0, None

@@ -3,7 +3,8 @@
 // same events as tools/probe/stream_probe.hip, to separate kernel cost from harness cost.
 // Build: hipcc -O3 --offload-arch=gfx950 -Iinclude -Iudpdk_amd/csrc [-DUDPDK_EXP_...]
 //        -o tools/probe/classify_probe tools/probe/classify_probe.hip
-#include "../../udpdk_amd/csrc/rx_kernels.hip"
+#include "../../udpdk_amd/csrc/rx_classify.hip"
+#include "../../udpdk_amd/csrc/rx_lanes.hip"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -161,7 +162,7 @@ int main()
         b.length = len + (size_t)(i % COPIES) * N;
         const int k = i % NS;
         b.meta = metak[k]; b.hist = histk[k]; b.tile_cnt = tcntk[k];
-        hipLaunchKernelGGL(rx_classify, dim3(tiles), dim3(CLS_BLOCK), lds, ss[k], b);
+        hipLaunchKernelGGL((rx_classify<1, 0, 1>), dim3(tiles), dim3(CLS_BLOCK), lds, ss[k], b);
         if (getenv("COMPACT")) {              // the single-lane compaction after it, same stream
             Compact1Args ca;
             ca.meta = b.meta; ca.tile_count = b.hist; ca.lane_pkt = lpk[k];

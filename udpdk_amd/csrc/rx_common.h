@@ -6,9 +6,8 @@
 
 namespace udpdk {
 
-constexpr int RX_BLOCK  = 256;              // rx_classify workgroup (4 waves)
-constexpr int RX_WAVES  = RX_BLOCK / 64;
-constexpr int RX_UNROLL = 4;                // 16-byte chunk loads in flight per lane
+constexpr int RX_BLOCK  = 256;              // rx_compact1 workgroup (4 waves)
+constexpr int RX_WAVES  = RX_BLOCK / 64;    // rx_compact1: each wave takes a quarter of the tile
 #ifndef UDPDK_RX_ROUND
 #define UDPDK_RX_ROUND 1024
 #endif
@@ -34,8 +33,6 @@ constexpr int SCAN_BLOCK = 256;
 constexpr int SCAN_TOP_BLOCK = 1024;
 constexpr uint32_t COMPACT1_DIRECT_TILES = 4096; // rx_compact1 sums its predecessors' counts itself
 constexpr uint32_t SCAN_COL_CHUNK = 32;     // tiles per chunk of the 3-pass column scan
-constexpr uint32_t SCAN_SMALL_MAX = 16384;  // single-workgroup scan up to this many elements
-constexpr uint32_t SCAN_SMALL_TILES = 32;   // ... and this many tiles (serial per lane)
 
 constexpr int TX_BLOCK = 256;
 

@@ -19,14 +19,14 @@
 #include <stdint.h>
 #include "udpdk_gpu.h"
 #include "rx_common.h"
+#include "wave.h"
 
 namespace udpdk {
 
 __global__ void __launch_bounds__(GATHER_BLOCK) rx_gather(GatherArgs a)
 {
-    const __amdgpu_buffer_rsrc_t fr =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(a.frames), (short)0, (int)a.rsrc_bytes, 0x00020000);
-    const uint32_t lane = __lane_id();
+    const __amdgpu_buffer_rsrc_t fr = make_rsrc(a.frames, a.rsrc_bytes);
+    const uint32_t lane = lane_id();
     for (uint32_t k = blockIdx.x * GATHER_BLOCK + threadIdx.x; k - threadIdx.x < a.count;
          k += gridDim.x * GATHER_BLOCK) {
         const bool valid = k < a.count;
@@ -45,8 +45,8 @@ __global__ void __launch_bounds__(GATHER_BLOCK) rx_gather(GatherArgs a)
 #pragma unroll
         for (uint32_t u = 0; u < 6; ++u) {
             const uint32_t off = 16u * u < need ? (X & ~3u) + 16u * u : 0x80000000u;
-            const auto x = __builtin_amdgcn_raw_buffer_load_b128(fr, (int)off, 0, 0);
-            D[4 * u] = x[0]; D[4 * u + 1] = x[1]; D[4 * u + 2] = x[2]; D[4 * u + 3] = x[3];
+            const uint4 x = load16(fr, off);
+            D[4 * u] = x.x; D[4 * u + 1] = x.y; D[4 * u + 2] = x.z; D[4 * u + 3] = x.w;
         }
         uint32_t W[20];                                          // W[m] = frame bytes 26 + 4m ..
 #pragma unroll
@@ -55,8 +55,7 @@ __global__ void __launch_bounds__(GATHER_BLOCK) rx_gather(GatherArgs a)
         uint4 v0[4];
 #pragma unroll
         for (uint32_t u = 0; u < 4; ++u) v0[u] = make_uint4(W[4 + 4 * u], W[5 + 4 * u], W[6 + 4 * u], W[7 + 4 * u]);
-        const uint32_t dlr = h[3] & 0xFFFFu;                                           // dgram_len, BE
-        const uint32_t dl = ((dlr & 0xFFu) << 8) | (dlr >> 8);
+        const uint32_t dl = bswap16(h[3]);                       // dgram_len, BE
         const uint32_t pl = (dl - 8u) & 0xFFFFu;                 // uint16_t dgram_payl_len (:436)
         const uint32_t seg = len >= 42u ? len - 42u : 0u;        // data_len - offset_payload (:458)
         const uint32_t so32 = valid && a.slot_off ? a.slot_off[k] : 0u;
@@ -79,10 +78,7 @@ __global__ void __launch_bounds__(GATHER_BLOCK) rx_gather(GatherArgs a)
                     for (uint32_t u = 0; u < 4; ++u) v[u] = v0[u];
                 } else {
 #pragma unroll
-                    for (uint32_t u = 0; u < 4; ++u) {
-                        const auto x = __builtin_amdgcn_raw_buffer_load_b128(fr, (int)(o + 42u + c + 16u * u), 0, 0);
-                        v[u] = make_uint4(x[0], x[1], x[2], x[3]);
-                    }
+                    for (uint32_t u = 0; u < 4; ++u) v[u] = load16(fr, o + 42u + c + 16u * u);
                 }
 #pragma unroll
                 for (uint32_t u = 0; u < 4; ++u)
@@ -120,11 +116,8 @@ __global__ void __launch_bounds__(GATHER_BLOCK) rx_gather(GatherArgs a)
                             const uint32_t sa = (oj[u] + 42u + b) & ~3u;
                             // (a piece just past the payload still loads when the piece before
                             // it needs its first dword)
-                            const auto x = __builtin_amdgcn_raw_buffer_load_b128(
-                                fr, (int)(b < nj[u] + (sh[u] != 0u ? 16u : 0u) ? sa : 0x80000000u), 0, 0);
-                            v[u][h2] = make_uint4(x[0], x[1], x[2], x[3]);
-                            e[u][h2] = __builtin_amdgcn_raw_buffer_load_b32(
-                                fr, (int)(lane == 63u && sh[u] != 0u && b < nj[u] ? sa + 16u : 0x80000000u), 0, 0);
+                            v[u][h2] = load16(fr, b < nj[u] + (sh[u] != 0u ? 16u : 0u) ? sa : 0x80000000u);
+                            e[u][h2] = load4(fr, lane == 63u && sh[u] != 0u && b < nj[u] ? sa + 16u : 0x80000000u);
                         }
 #pragma unroll
                     for (uint32_t u = 0; u < 2; ++u)

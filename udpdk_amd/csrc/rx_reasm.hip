@@ -59,6 +59,7 @@
 
 #include "udpdk_gpu.h"
 #include "rx_common.h"
+#include "wave.h"
 
 namespace udpdk {
 
@@ -195,30 +196,6 @@ __device__ __forceinline__ void st_a(T *p, T v)
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void *p, uint32_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), (short)0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ uint32_t ld32(__amdgpu_buffer_rsrc_t r, uint32_t off)
-{
-    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0);
-}
-
-__device__ __forceinline__ uint4 load16(__amdgpu_buffer_rsrc_t r, uint32_t off)
-{
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-
-__device__ __forceinline__ void store16(__amdgpu_buffer_rsrc_t r, uint32_t off, uint4 v)
-{
-    __attribute__((ext_vector_type(4))) uint32_t x = {v.x, v.y, v.z, v.w};
-    __builtin_amdgcn_raw_buffer_store_b128(x, r, (int)off, 0, 0);
-}
-
-__device__ __forceinline__ uint32_t bswap16(uint32_t x) { return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu); }
-
 // crc32c (reflected, poly 0x82F63B78) of one dword, a byte at a time from a 256-entry table of
 // the byte steps in LDS (crc_table_init): 4 lookups instead of 32 dependent bit steps (the
 // bit-serial form was ~450 VALU instructions per fragment, a sixth of the run test's kernel).
@@ -250,13 +227,13 @@ __device__ __forceinline__ FragHdr frag_hdr(const ReasmArgs &a, __amdgpu_buffer_
 {
     const uint32_t o = a.offset[i];
     FragHdr h;
-    const uint32_t w16 = ld32(fr, o + 16);   // total length | id
-    const uint32_t w20 = ld32(fr, o + 20);   // fragment field | ttl | proto
+    const uint32_t w16 = load4(fr, o + 16);   // total length | id
+    const uint32_t w20 = load4(fr, o + 20);   // fragment field | ttl | proto
     h.tl = bswap16(w16 & 0xFFFFu);
     h.id = w16 >> 16;
     h.ff = bswap16(w20 & 0xFFFFu);
-    h.src = ld32(fr, o + 26);
-    h.dst = ld32(fr, o + 30);
+    h.src = load4(fr, o + 26);
+    h.dst = load4(fr, o + 30);
     h.flen = a.length[i];
     return h;
 }
@@ -267,12 +244,12 @@ __device__ void wave_copy(uint8_t *dst, __amdgpu_buffer_rsrc_t r, uint32_t src_o
 {
     const uint32_t lane = __lane_id();
     const uint32_t head = std::min<uint32_t>((4u - ((uint32_t)(uintptr_t)dst & 3u)) & 3u, len);
-    if (lane < head) dst[lane] = (uint8_t)ld32(r, src_off + lane);
+    if (lane < head) dst[lane] = (uint8_t)load4(r, src_off + lane);
     const uint32_t body = (len - head) >> 2;
     uint32_t *d32 = reinterpret_cast<uint32_t *>(dst + head);
-    for (uint32_t k = lane; k < body; k += 64) d32[k] = ld32(r, src_off + head + 4u * k);
+    for (uint32_t k = lane; k < body; k += 64) d32[k] = load4(r, src_off + head + 4u * k);
     const uint32_t tail = len - head - 4u * body;
-    if (lane < tail) dst[head + 4u * body + lane] = (uint8_t)ld32(r, src_off + head + 4u * body + lane);
+    if (lane < tail) dst[head + 4u * body + lane] = (uint8_t)load4(r, src_off + head + 4u * body + lane);
 }
 
 // As wave_copy, with 16-byte stores once the destination is 16-byte aligned (byte-aligned
@@ -281,7 +258,7 @@ __device__ void wave_copy16(uint8_t *dst, __amdgpu_buffer_rsrc_t r, uint32_t src
 {
     const uint32_t lane = __lane_id();
     const uint32_t head = std::min<uint32_t>((16u - ((uint32_t)(uintptr_t)dst & 15u)) & 15u, len);
-    if (lane < head) dst[lane] = (uint8_t)ld32(r, src_off + lane);
+    if (lane < head) dst[lane] = (uint8_t)load4(r, src_off + lane);
     const uint32_t body = (len - head) >> 4;
     uint4 *d16 = reinterpret_cast<uint4 *>(dst + head);
     const uint32_t sb = src_off + head;
@@ -290,10 +267,7 @@ __device__ void wave_copy16(uint8_t *dst, __amdgpu_buffer_rsrc_t r, uint32_t src
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const uint32_t k = k0 + 64u * u;
-            if (k < body) {
-                const auto x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(sb + 16u * k), 0, 0);
-                v[u] = make_uint4(x[0], x[1], x[2], x[3]);
-            }
+            if (k < body) v[u] = load16(r, sb + 16u * k);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -302,7 +276,7 @@ __device__ void wave_copy16(uint8_t *dst, __amdgpu_buffer_rsrc_t r, uint32_t src
         }
     }
     const uint32_t done = head + 16u * body, tail = len - done;
-    if (lane < tail) dst[done + lane] = (uint8_t)ld32(r, src_off + done + lane);
+    if (lane < tail) dst[done + lane] = (uint8_t)load4(r, src_off + done + lane);
 }
 
 } // namespace
@@ -404,7 +378,7 @@ __global__ void __launch_bounds__(RS_BLOCK) reasm_prep(ReasmArgs a, uint32_t F)
     __shared__ uint32_t crc_tab[256];
     crc_table_init(crc_tab);
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t fr = rsrc(a.frames, a.rsrc_bytes);
+    const __amdgpu_buffer_rsrc_t fr = make_rsrc(a.frames, a.rsrc_bytes);
     for (uint32_t p = blockIdx.x * RS_BLOCK + threadIdx.x; p < F; p += gridDim.x * RS_BLOCK) {
         const uint32_t i = a.order[p];
         prep_record(a, crc_tab, p, i, frag_hdr(a, fr, i));
@@ -465,11 +439,11 @@ __device__ __forceinline__ void run_insert(const ReasmArgs &a, uint32_t id, uint
 // (id, index) then by src | dst: 38 + 64 key bits against 2 ib).
 __global__ void __launch_bounds__(RS_BLOCK) reasm_group(ReasmArgs a, uint32_t F)
 {
-    const __amdgpu_buffer_rsrc_t fr = rsrc(a.frames, a.rsrc_bytes);
+    const __amdgpu_buffer_rsrc_t fr = make_rsrc(a.frames, a.rsrc_bytes);
     const unsigned long long tag = (unsigned long long)a.hset_tag << 48;
     for (uint32_t p = blockIdx.x * RS_BLOCK + threadIdx.x; p < F; p += gridDim.x * RS_BLOCK) {
         const uint32_t o = a.offset[a.frag_list[p]];
-        const uint32_t id = ld32(fr, o + 16) >> 16, src = ld32(fr, o + 26), dst = ld32(fr, o + 30);
+        const uint32_t id = load4(fr, o + 16) >> 16, src = load4(fr, o + 26), dst = load4(fr, o + 30);
         const unsigned long long fp = run_fp(id, src, dst);
         const unsigned long long fpb = ((fp >> 40) & 0xFFFFFFull) << 24;
         const unsigned long long val = tag | fpb | p;
@@ -485,7 +459,7 @@ __global__ void __launch_bounds__(RS_BLOCK) reasm_group(ReasmArgs a, uint32_t F)
             if ((cur & (0xFFFFFFull << 24)) == fpb) {
                 const uint32_t q = (uint32_t)(cur & 0xFFFFFFull);
                 const uint32_t oq = a.offset[a.frag_list[q]];
-                if ((ld32(fr, oq + 16) >> 16) == id && ld32(fr, oq + 26) == src && ld32(fr, oq + 30) == dst) {
+                if ((load4(fr, oq + 16) >> 16) == id && load4(fr, oq + 26) == src && load4(fr, oq + 30) == dst) {
                     group = q;                                         // the key's group
                     break;
                 }
@@ -499,32 +473,6 @@ __global__ void __launch_bounds__(RS_BLOCK) reasm_group(ReasmArgs a, uint32_t F)
 }
 
 namespace {
-
-// Orders a wave's LDS accesses across lanes (DS instructions of one wave execute in order).
-__device__ __forceinline__ void wave_sync_rs()
-{
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// Every store this wave issued has completed (CDNA counts stores in vmcnt).
-__device__ __forceinline__ void stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// Exclusive prefix sum of v over the wave's lanes; *total gets the wave's sum. Called with every
-// lane active (wave-uniform control flow). On the DPP network: six VALU ops and a readlane, where
-// the __shfl_up form made seven ds_bpermute round trips through the LDS pipeline.
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t *total)
-{
-    uint32_t x = v;
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);   // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);   // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);   // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);   // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    *total = (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-    return x - v;
-}
 
 // Fresh flow state (ip_frag_reset / ip_frag_tbl_add) for the key.
 __device__ __forceinline__ void state_reset(uint32_t *st, uint32_t src, uint32_t dst, uint32_t id,
@@ -1232,7 +1180,7 @@ __global__ void __launch_bounds__(64) reasm_serial(ReasmArgs a, const uint32_t *
             --use;
             head_ok = false;
             stores_done();
-            wave_sync_rs();
+            wave_sync();
         }
         const uint32_t cl = (uint32_t)__ffsll((long long)pick) - 1u;
         const uint32_t cand = __shfl(slot, cl, 64);
@@ -1240,7 +1188,7 @@ __global__ void __launch_bounds__(64) reasm_serial(ReasmArgs a, const uint32_t *
 #pragma unroll
             for (uint32_t j = 0; j < E_WORDS; ++j) st[j] = w[j];
         }
-        wave_sync_rs();
+        wave_sync();
         uint32_t inval = 0, moved = 0;
         if (lane == 0) {
             bool fresh = !mm;                                // ip_frag_tbl_add (after del if stale)
@@ -1289,7 +1237,7 @@ __global__ void __launch_bounds__(64) reasm_serial(ReasmArgs a, const uint32_t *
                 inval = 1;
             }
         }
-        wave_sync_rs();
+        wave_sync();
         inval = __shfl(inval, 0, 64);
         moved = __shfl(moved, 0, 64);
         if (!mm && !ms) ++use;                               // an empty entry taken
@@ -1302,7 +1250,7 @@ __global__ void __launch_bounds__(64) reasm_serial(ReasmArgs a, const uint32_t *
             st_a(e + lane, st[lane]);
         }
         stores_done();
-        wave_sync_rs();
+        wave_sync();
     }
     if (lane == 0) {
         if (comp) atomicAdd(a.tab_used, use - use0);     // (wraps for a net release)
@@ -1799,7 +1747,7 @@ __global__ void __launch_bounds__(RS_BLOCK) reasm_scan(ReasmArgs a)
     for (uint32_t x = lane; x < 2u * RS_SCAN_PW; x += 64u) w_ht[w][x] = 0xFFFFFFFFu;
     __syncthreads();
     if (s_ug) return;                                             // the whole block
-    const __amdgpu_buffer_rsrc_t fr = rsrc(a.frames, a.rsrc_bytes);
+    const __amdgpu_buffer_rsrc_t fr = make_rsrc(a.frames, a.rsrc_bytes);
     const uint32_t wb = b * RS_CL + w * RS_SCAN_PW;
     constexpr uint32_t OOR = 0x80000000u;
     // the two slots' fragments, each level of the chains (list, offset, header) in one round trip
@@ -1818,15 +1766,15 @@ __global__ void __launch_bounds__(RS_BLOCK) reasm_scan(ReasmArgs a)
     const uint32_t op = prev ? a.offset[ip] : 0u;
 #pragma unroll
     for (uint32_t k = 0; k < 2; ++k) {
-        w16[k] = ld32(fr, o[k] + 16);
-        w20[k] = ld32(fr, o[k] + 20);
-        src[k] = ld32(fr, o[k] + 26);
-        dst[k] = ld32(fr, o[k] + 30);
+        w16[k] = load4(fr, o[k] + 16);
+        w20[k] = load4(fr, o[k] + 20);
+        src[k] = load4(fr, o[k] + 26);
+        dst[k] = load4(fr, o[k] + 30);
         fl[k] = a.length[i[k]];
         id[k] = w16[k] >> 16;
     }
-    const uint32_t pw16 = ld32(fr, prev ? op + 16 : OOR), pws = ld32(fr, prev ? op + 26 : OOR),
-                   pwd = ld32(fr, prev ? op + 30 : OOR);
+    const uint32_t pw16 = load4(fr, prev ? op + 16 : OOR), pws = load4(fr, prev ? op + 26 : OOR),
+                   pwd = load4(fr, prev ? op + 30 : OOR);
     bool start[2];
     {
         uint32_t pid = __shfl_up(id[0], 1, 64), ps = __shfl_up(src[0], 1, 64), pd = __shfl_up(dst[0], 1, 64);
@@ -1864,7 +1812,7 @@ __global__ void __launch_bounds__(RS_BLOCK) reasm_scan(ReasmArgs a)
             w_id[w][rank[k]] = id[k];
         }
     }
-    wave_sync_rs();
+    wave_sync();
     // Two runs of one key in the wave's positions: the batch is not grouped (interleaved flows
     // show it here, long before reasm_ec's run test), and nothing but the fragment list is needed
     // from this launch. Insert-or-find of each run's key in an LDS table by rank.
@@ -1935,7 +1883,7 @@ __global__ void __launch_bounds__(RS_BLOCK) reasm_scan(ReasmArgs a)
             a.pflag[p] = 0u;
         }
     }
-    wave_sync_rs();
+    wave_sync();
     const bool limit = a.max_entries < a.entries;
 #pragma unroll 1
     for (uint32_t j = lane; j < ((S + 63u) & ~63u); j += 64u) {   // wave-uniform trip count
@@ -1970,8 +1918,8 @@ __global__ void __launch_bounds__(RS_BLOCK) reasm_scan(ReasmArgs a)
                     while ((a.meta[fi] & 0xFu) != UDPDK_V_FRAG) ++fi;
                 }
                 fo = a.offset[fi];
-                const uint32_t x16 = ld32(fr, fo + 16), x20 = ld32(fr, fo + 20), xs = ld32(fr, fo + 26),
-                               xd = ld32(fr, fo + 30);
+                const uint32_t x16 = load4(fr, fo + 16), x20 = load4(fr, fo + 20), xs = load4(fr, fo + 26),
+                               xd = load4(fr, fo + 30);
                 if ((x16 >> 16) != kid || xs != ksrc || xd != kdst) break;
                 FragHdr h;
                 h.src = xs;
@@ -2172,7 +2120,7 @@ __device__ __forceinline__ void emit_copy(const EmitArgs &a, uint32_t C)
     // the wave index as a scalar: the datagram record and everything derived from it are
     // wave-uniform scalar loads and SGPRs, not per-lane copies
     const uint32_t lane = __lane_id(), w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const __amdgpu_buffer_rsrc_t fr = rsrc(a.frames, a.rsrc_bytes);
+    const __amdgpu_buffer_rsrc_t fr = make_rsrc(a.frames, a.rsrc_bytes);
     // The next datagram's record and output offset are loaded while this one is copied.
     const uint32_t stride = gridDim.x * RS_WAVES;
     uint32_t k = blockIdx.x * RS_WAVES + w;
@@ -2192,8 +2140,8 @@ __device__ __forceinline__ void emit_copy(const EmitArgs &a, uint32_t C)
         }
         const uint32_t L = 34u + r.total;
         const uint8_t *eb = a.ebuf + (size_t)r.entry * a.stride;
-        const __amdgpu_buffer_rsrc_t er = rsrc(eb, a.stride);
-        const __amdgpu_buffer_rsrc_t orr = rsrc(a.out + oo, (L + 15u) & ~15u);
+        const __amdgpu_buffer_rsrc_t er = make_rsrc(eb, a.stride);
+        const __amdgpu_buffer_rsrc_t orr = make_rsrc(a.out + oo, (L + 15u) & ~15u);
         // segments: destination start d0, end d1, source offset of d0 (s0), held
         uint32_t d0[RS_MAX_FRAG], d1[RS_MAX_FRAG], s0[RS_MAX_FRAG];
         bool held[RS_MAX_FRAG];
@@ -2237,12 +2185,12 @@ __device__ __forceinline__ void emit_copy(const EmitArgs &a, uint32_t C)
             uint32_t hi;
             if (!mixed) {
                 x = load16(one, want ? sa : OOR);
-                hi = ld32(one, want && sh ? sa + 16u : OOR);
+                hi = load4(one, want && sh ? sa + 16u : OOR);
             } else {
                 const bool h = pickb(q);
                 const uint4 x1 = load16(er, want && h ? sa : OOR), x2 = load16(fr, want && !h ? sa : OOR);
                 x = make_uint4(x1.x | x2.x, x1.y | x2.y, x1.z | x2.z, x1.w | x2.w);
-                hi = ld32(er, want && h && sh ? sa + 16u : OOR) | ld32(fr, want && !h && sh ? sa + 16u : OOR);
+                hi = load4(er, want && h && sh ? sa + 16u : OOR) | load4(fr, want && !h && sh ? sa + 16u : OOR);
             }
             return funnel4(x, hi, sh);
         };
@@ -2343,7 +2291,7 @@ __device__ __forceinline__ void store_part(__amdgpu_buffer_rsrc_t r, uint32_t D,
 __device__ __forceinline__ void emit_inplace(const EmitArgs &a, uint8_t *frames, uint32_t C)
 {
     const uint32_t lane = __lane_id(), w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const __amdgpu_buffer_rsrc_t fr = rsrc(frames, a.rsrc_bytes);
+    const __amdgpu_buffer_rsrc_t fr = make_rsrc(frames, a.rsrc_bytes);
     constexpr uint32_t OOR = 0x80000000u;
     const uint32_t stride = gridDim.x * RS_WAVES;
     uint32_t k = blockIdx.x * RS_WAVES + w;
@@ -2401,7 +2349,7 @@ __device__ __forceinline__ void emit_inplace(const EmitArgs &a, uint8_t *frames,
             const bool in = on && c < g.nch;
             const uint32_t S = g.D0 + 16u * c + g.shift, sa = S & ~3u;
             g.x[u] = load16(fr, in ? sa : OOR);
-            g.hi[u] = ld32(fr, in && (S & 3u) ? sa + 16u : OOR);
+            g.hi[u] = load4(fr, in && (S & 3u) ? sa + 16u : OOR);
         }
         g.orig = load16(fr, on && lane == 0u ? g.D0 : OOR);
     };
@@ -2473,7 +2421,7 @@ __device__ __forceinline__ void emit_inplace(const EmitArgs &a, uint8_t *frames,
                         Dv[u] = D0 + 16u * c;
                         const uint32_t S = Dv[u] + shift, sa = S & ~3u, sh = S & 3u;
                         const uint4 x = load16(fr, inv[u] ? sa : OOR);
-                        const uint32_t hi = ld32(fr, inv[u] && sh ? sa + 16u : OOR);
+                        const uint32_t hi = load4(fr, inv[u] && sh ? sa + 16u : OOR);
                         v[u] = funnel4(x, hi, sh);
                     }
 #pragma unroll
@@ -2584,7 +2532,7 @@ struct StoreArgs {
 __global__ void __launch_bounds__(RS_BLOCK) reasm_store(StoreArgs a)
 {
     const uint32_t w = threadIdx.x >> 6;
-    const __amdgpu_buffer_rsrc_t fr = rsrc(a.frames, a.rsrc_bytes);
+    const __amdgpu_buffer_rsrc_t fr = make_rsrc(a.frames, a.rsrc_bytes);
     for (uint32_t k = blockIdx.x * RS_WAVES + w; k < a.J; k += gridDim.x * RS_WAVES) {
         const ReasmJob jb = a.jobs[k];
         if (jb.frame == RS_NONE) continue;

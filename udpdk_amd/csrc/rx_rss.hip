@@ -22,42 +22,11 @@
 
 #include "udpdk_gpu.h"
 #include "rx_common.h"
+#include "wave.h"
 
 namespace udpdk {
 
 namespace {
-
-// Orders a wave's LDS accesses across lanes (its DS instructions execute in order).
-__device__ __forceinline__ void wsync()
-{
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// Lanes of the wave holding the same key (key < 2^bits), from one ballot per key bit.
-// Inclusive wave64 prefix sum on the DPP network (every lane active): six VALU ops where the
-// __shfl_up chain made six ds_bpermute round trips
-__device__ __forceinline__ uint32_t rss_scan_dpp(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long peers_of(uint32_t key, uint32_t bits, bool active)
-{
-    unsigned long long peers = __ballot(active);
-    for (uint32_t b = 0; b < bits; ++b) {
-        const bool kb = (key >> b) & 1u;
-        const unsigned long long bal = __ballot(kb);
-        peers &= kb ? bal : ~bal;
-    }
-    return peers;
-}
 
 // The fused form of rss_base, run by the last rss_hash workgroup (RssArgs::fuse): the same
 // exclusive scan of the queue-major histogram as one array, in passes of 32 entries per thread
@@ -66,8 +35,8 @@ __device__ __forceinline__ unsigned long long peers_of(uint32_t key, uint32_t bi
 __device__ void rss_scan_last(uint32_t *hist, uint32_t n, uint32_t T, uint32_t *queue_off, uint32_t *total)
 {
     __shared__ uint32_t wsum[RSS_BLOCK / 64];
-    const uint32_t tid = threadIdx.x, lane = __lane_id(), w = tid >> 6;
-    const __amdgpu_buffer_rsrc_t hr = __builtin_amdgcn_make_buffer_rsrc(hist, (short)0, (int)(4u * n), 0x00020000);
+    const uint32_t tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+    const __amdgpu_buffer_rsrc_t hr = make_rsrc(hist, 4u * n);
     constexpr uint32_t PER = 32;
     uint32_t carry = 0;
     for (uint32_t b0 = 0; b0 < n; b0 += PER * RSS_BLOCK) {
@@ -75,14 +44,14 @@ __device__ void rss_scan_last(uint32_t *hist, uint32_t n, uint32_t T, uint32_t *
         uint32_t v[PER];
 #pragma unroll
         for (uint32_t i = 0; i < PER / 4u; ++i) {
-            const uint4 q = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(hr, (int)(4u * k0 + 16u * i), 0, 16));
+            const uint4 q = load16<AUX_SC1>(hr, 4u * k0 + 16u * i);
             v[4 * i] = q.x; v[4 * i + 1] = q.y; v[4 * i + 2] = q.z; v[4 * i + 3] = q.w;
         }
         uint32_t sum = 0;
 #pragma unroll
         for (uint32_t i = 0; i < PER; ++i) sum += v[i];
         uint32_t incl = sum;
-        incl = rss_scan_dpp(incl);
+        incl = wave_incl_scan(incl);
         if (lane == 63) wsum[w] = incl;
         __syncthreads();
         uint32_t run = carry + incl - sum, grand = 0;
@@ -104,9 +73,7 @@ __device__ void rss_scan_last(uint32_t *hist, uint32_t n, uint32_t T, uint32_t *
         }
 #pragma unroll
         for (uint32_t i = 0; i < PER / 4u; ++i)
-            __builtin_amdgcn_raw_buffer_store_b128(
-                __builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3])),
-                hr, (int)(4u * k0 + 16u * i), 0, 0);
+            store16(hr, 4u * k0 + 16u * i, make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]));
         carry += grand;
         __syncthreads();                                   // wsum read by every wave
     }
@@ -123,9 +90,8 @@ __global__ void __launch_bounds__(RSS_BLOCK) rss_hash(RssArgs a)
     __shared__ __attribute__((aligned(16))) uint32_t tab[12][256];
     __shared__ uint16_t reta[RSS_RETA_MAX];
     __shared__ uint32_t hist[RSS_MAX_QUEUES];
-    const uint32_t tid = threadIdx.x, lane = __lane_id();
-    const __amdgpu_buffer_rsrc_t fr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(a.frames), (short)0, (int)a.rsrc_bytes, 0x00020000);
+    const uint32_t tid = threadIdx.x, lane = lane_id();
+    const __amdgpu_buffer_rsrc_t fr = make_rsrc(a.frames, a.rsrc_bytes);
     const uint32_t tile = blockIdx.x;
     const uint32_t t0 = tile * RSS_TILE, t1 = min(a.n, t0 + RSS_TILE);
     constexpr uint32_t STEPS = RSS_TILE / RSS_BLOCK;
@@ -154,8 +120,8 @@ __global__ void __launch_bounds__(RSS_BLOCK) rss_hash(RssArgs a)
     for (uint32_t s = 0; s < STEPS; ++s) {
         const bool ok = (uint64_t)o[s] + len[s] <= a.frames_bytes && len[s] >= 34u;
         const uint32_t A = ok ? (o[s] + 12u) & ~3u : 0u;
-        h0[s] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(fr, (int)A, 0, 0));
-        h1[s] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(fr, (int)(A + 16u), 0, 0));
+        h0[s] = load16(fr, A);
+        h1[s] = load16(fr, A + 16u);
     }
     {
         uint4 *dst = reinterpret_cast<uint4 *>(&tab[0][0]);
@@ -182,7 +148,7 @@ __global__ void __launch_bounds__(RSS_BLOCK) rss_hash(RssArgs a)
         const uint32_t ports = (g[5] >> 16) | (g[6] << 16);       // used only when len >= 38
         const uint32_t pt = ok ? (a.ptype ? a.ptype[i] : ((w12 & 0xFFFFu) == 0x0008u ? 0x211u : 0x1u)) : 0u;
         if (ok && (pt & 0x10u)) {
-            const uint32_t ff = ((w20 & 0xFFu) << 8) | ((w20 >> 8) & 0xFFu);
+            const uint32_t ff = bswap16(w20);
             const bool frag = (ff & 0x3FFFu) != 0u;
             const bool udp4 = !frag && ((w20 >> 24) & 0xFFu) == 17u && len[s] >= 38u && (a.hash_types & 2u);
             if (udp4 || (a.hash_types & 1u)) {
@@ -200,7 +166,7 @@ __global__ void __launch_bounds__(RSS_BLOCK) rss_hash(RssArgs a)
             a.hash[i] = hash;
             a.qid[i] = (uint8_t)q;
         }
-        const unsigned long long peers = peers_of(q, a.q_bits, in);
+        const unsigned long long peers = wave_peers(q, a.q_bits, in);
         if (in && lane == (uint32_t)__ffsll((long long)peers) - 1u)
             atomicAdd(&hist[q], (uint32_t)__popcll(peers));
     }
@@ -215,7 +181,7 @@ __global__ void __launch_bounds__(RSS_BLOCK) rss_hash(RssArgs a)
     __shared__ uint32_t last;
     for (uint32_t q = tid; q < a.n_queues; q += RSS_BLOCK)
         __hip_atomic_store(&a.hist[(size_t)q * a.n_tiles + tile], hist[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stores_done();
     __syncthreads();
     if (tid == 0) {
         unsigned long long fin;
@@ -224,7 +190,7 @@ __global__ void __launch_bounds__(RSS_BLOCK) rss_hash(RssArgs a)
     __syncthreads();
     if (!last) return;
     if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stores_done();
     __syncthreads();
     rss_scan_last(a.hist, a.n_queues * a.n_tiles, a.n_tiles, a.queue_off, a.total);
 }
@@ -241,21 +207,21 @@ rss_base(uint32_t *hist, uint32_t n, uint32_t T, uint32_t *queue_off, uint32_t *
 {
     constexpr uint32_t PER = RSS_BASE_MAX / 1024u;
     __shared__ uint32_t wsum[16];
-    const uint32_t tid = threadIdx.x, lane = __lane_id(), w = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
     // range-checked per dword: entries past n read as 0 and are never written
-    const __amdgpu_buffer_rsrc_t hr = __builtin_amdgcn_make_buffer_rsrc(hist, (short)0, (int)(4u * n), 0x00020000);
+    const __amdgpu_buffer_rsrc_t hr = make_rsrc(hist, 4u * n);
     const uint32_t k0 = PER * tid;
     uint32_t v[PER];
 #pragma unroll
     for (uint32_t i = 0; i < PER / 4u; ++i) {
-        const uint4 q = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(hr, (int)(4u * k0 + 16u * i), 0, 0));
+        const uint4 q = load16(hr, 4u * k0 + 16u * i);
         v[4 * i] = q.x; v[4 * i + 1] = q.y; v[4 * i + 2] = q.z; v[4 * i + 3] = q.w;
     }
     uint32_t sum = 0;
 #pragma unroll
     for (uint32_t i = 0; i < PER; ++i) sum += v[i];
     uint32_t incl = sum;
-    incl = rss_scan_dpp(incl);
+    incl = wave_incl_scan(incl);
     if (lane == 63) wsum[w] = incl;
     __syncthreads();
     uint32_t run = incl - sum, grand = 0;
@@ -278,9 +244,7 @@ rss_base(uint32_t *hist, uint32_t n, uint32_t T, uint32_t *queue_off, uint32_t *
     }
 #pragma unroll
     for (uint32_t i = 0; i < PER / 4u; ++i)
-        __builtin_amdgcn_raw_buffer_store_b128(
-            __builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3])),
-            hr, (int)(4u * k0 + 16u * i), 0, 0);
+        store16(hr, 4u * k0 + 16u * i, make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]));
     if (tid == 0) {
         queue_off[n / T] = grand;
         *total = grand;
@@ -292,7 +256,7 @@ rss_base(uint32_t *hist, uint32_t n, uint32_t T, uint32_t *queue_off, uint32_t *
 __global__ void __launch_bounds__(RSS_BLOCK) rss_scatter(RssArgs a)
 {
     __shared__ uint32_t cnt[RSS_BLOCK / 64][RSS_MAX_QUEUES], run[RSS_BLOCK / 64][RSS_MAX_QUEUES];
-    const uint32_t tid = threadIdx.x, lane = __lane_id(), w = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
     const uint32_t t0 = blockIdx.x * RSS_TILE, t1 = min(a.n, t0 + RSS_TILE);
     const uint32_t wb = t0 + w * (RSS_TILE / (RSS_BLOCK / 64));
     constexpr uint32_t STEPS = RSS_TILE / RSS_BLOCK;
@@ -303,13 +267,13 @@ __global__ void __launch_bounds__(RSS_BLOCK) rss_scatter(RssArgs a)
         const uint32_t i = wb + 64u * s + lane;
         qv[s] = i < t1 ? a.qid[i] : 0u;
     }
-    wsync();
+    wave_sync();
 #pragma unroll
     for (uint32_t s = 0; s < STEPS; ++s) {
         const uint32_t i = wb + 64u * s + lane;
-        const unsigned long long peers = peers_of(qv[s], a.q_bits, i < t1);
+        const unsigned long long peers = wave_peers(qv[s], a.q_bits, i < t1);
         if (i < t1 && lane == (uint32_t)__ffsll((long long)peers) - 1u) cnt[w][qv[s]] += (uint32_t)__popcll(peers);
-        wsync();
+        wave_sync();
     }
     __syncthreads();
     // running position per queue for this wave (row w of run[] is wave w's alone)
@@ -318,22 +282,22 @@ __global__ void __launch_bounds__(RSS_BLOCK) rss_scatter(RssArgs a)
         for (uint32_t v = 0; v < w; ++v) b += cnt[v][q];
         run[w][q] = b;
     }
-    wsync();
+    wave_sync();
     const unsigned long long lt = (1ull << lane) - 1ull;
 #pragma unroll
     for (uint32_t s = 0; s < STEPS; ++s) {
         const uint32_t i = wb + 64u * s + lane;
         const bool in = i < t1;
         const uint32_t q = qv[s];
-        const unsigned long long peers = peers_of(q, a.q_bits, in);
+        const unsigned long long peers = wave_peers(q, a.q_bits, in);
         const uint32_t base = in ? run[w][q] : 0u;
-        wsync();
+        wave_sync();
         if (in) {
             const uint32_t pos = base + (uint32_t)__popcll(peers & lt);
             a.queue_pkt[pos] = i;
             if (lane == (uint32_t)__ffsll((long long)peers) - 1u) run[w][q] = base + (uint32_t)__popcll(peers);
         }
-        wsync();
+        wave_sync();
     }
 }
 

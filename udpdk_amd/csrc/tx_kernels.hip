@@ -26,20 +26,23 @@
 
 #include "udpdk_gpu.h"
 #include "rx_common.h"
+#include "wave.h"
 
 namespace udpdk {
 
 namespace {
 
+// Not wave.h's wave_sync: a wavefront-scope fence, which also drains vmcnt.
 __device__ __forceinline__ void wave_sync_tx()
 {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
 
+// Not wave.h's wave_excl_scan: the __shfl_up chain (ds_bpermute), not the DPP network.
 __device__ __forceinline__ uint32_t excl_scan64(uint32_t v, uint32_t *total)
 {
-    const uint32_t lane = __lane_id();
+    const uint32_t lane = lane_id();
     uint32_t x = v;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -50,22 +53,11 @@ __device__ __forceinline__ uint32_t excl_scan64(uint32_t v, uint32_t *total)
     return x - v;
 }
 
-__device__ __forceinline__ uint32_t win_mask(int a, int e, int i)
-{
-    int la = min(max(a - 4 * i, 0), 4);
-    int le = min(max(e - 4 * i, 0), 4);
-    uint32_t hm = le >= 4 ? 0xFFFFFFFFu : ((1u << (8 * le)) - 1u);
-    uint32_t lm = la >= 4 ? 0xFFFFFFFFu : ((1u << (8 * la)) - 1u);
-    return hm & ~lm;
-}
-
 __device__ __forceinline__ uint32_t sel4(uint32_t d, uint32_t a0, uint32_t a1, uint32_t a2,
                                          uint32_t a3)
 {
     return d == 0 ? a0 : (d == 1 ? a1 : (d == 2 ? a2 : a3));
 }
-
-__device__ __forceinline__ uint32_t bswap16(uint32_t x) { return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu); }
 
 // Sum of the 20-byte IPv4 header built below (checksum field zero) as LE 16-bit words:
 // version/IHL 0x45, tos 0, total length tl, id 0, fragment field ff (host order), ttl 64,
@@ -99,10 +91,8 @@ constexpr uint32_t TX_SMALL_LOADS = (TX_SMALL_SPAN - 42u + 15u) / 16u;
 __device__ __forceinline__ void tx_small(const TxArgs &a, uint32_t i, uint32_t fo, uint32_t L,
                                          uint32_t po, int32_t sock)
 {
-    const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(a.payload), (short)0, (int)a.payload_rsrc, 0x00020000);
-    const __amdgpu_buffer_rsrc_t fw = __builtin_amdgcn_make_buffer_rsrc(
-        a.frames, (short)0, (int)a.frames_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t pr = make_rsrc(a.payload, a.payload_rsrc);
+    const __amdgpu_buffer_rsrc_t fw = make_rsrc(a.frames, a.frames_bytes);
     const uint32_t span = L + 42u;
     const bool ok = i < a.n && (uint64_t)fo + span <= a.frames_bytes &&
                     (uint64_t)po + L <= a.payload_bytes && sock >= 0 && (uint32_t)sock < a.n_slots;
@@ -113,8 +103,8 @@ __device__ __forceinline__ void tx_small(const TxArgs &a, uint32_t i, uint32_t f
         const bool need = ok && 16u * m < L;
         P[4 * m] = P[4 * m + 1] = P[4 * m + 2] = P[4 * m + 3] = 0u;
         if (__ballot(need)) {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(pr, (int)(need ? po + 16u * m : 0x80000000u), 0, 0);
-            P[4 * m] = v[0]; P[4 * m + 1] = v[1]; P[4 * m + 2] = v[2]; P[4 * m + 3] = v[3];
+            const uint4 v = load16(pr, need ? po + 16u * m : 0x80000000u);
+            P[4 * m] = v.x; P[4 * m + 1] = v.y; P[4 * m + 2] = v.z; P[4 * m + 3] = v.w;
         }
     }
     P[4 * TX_SMALL_LOADS] = 0u;
@@ -142,6 +132,7 @@ __device__ __forceinline__ void tx_small(const TxArgs &a, uint32_t i, uint32_t f
 #pragma unroll
     for (uint32_t c = 0; c < TX_SMALL_SPAN / 16; ++c) {
         if (16u * c + 16u <= span) {
+            // (the raw builtin, not store16: the braces fix the order the four words are built in)
             const __attribute__((ext_vector_type(4))) uint32_t v = {F(4 * c), F(4 * c + 1), F(4 * c + 2), F(4 * c + 3)};
             __builtin_amdgcn_raw_buffer_store_b128(v, fw, (int)(fo + 16u * c), 0, 0);
         } else if (16u * c < span) {
@@ -168,9 +159,8 @@ tx_build(TxArgs a)
     // per output frame of the current round
     // (l_len bit 31: 34-byte header, a fragment after the first)
     __shared__ uint32_t l_cs[TXW][64], l_fo[TXW][64], l_len[TXW][64], l_po[TXW][64];
-    const uint32_t lane = __lane_id(), w = threadIdx.x >> 6;
-    const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(a.payload), (short)0, (int)a.payload_rsrc, 0x00020000);
+    const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
+    const __amdgpu_buffer_rsrc_t pr = make_rsrc(a.payload, a.payload_rsrc);
     const uint32_t waves_total = gridDim.x * TXW;
     const uint32_t fpl = a.mtu ? a.mtu - 20u : 0u;      // IP payload bytes per full fragment
 
@@ -323,9 +313,8 @@ tx_build(TxArgs a)
                     const int64_t src0 = (int64_t)pq + r0c - hq;
                     const int64_t sa = src0 & ~(int64_t)15;
                     const uint32_t sft = (uint32_t)(src0 - sa);       // 0..15
-                    const auto v0 = __builtin_amdgcn_raw_buffer_load_b128(pr, (int)(uint32_t)sa, 0, 0);
-                    const auto v1 = __builtin_amdgcn_raw_buffer_load_b128(pr, (int)(uint32_t)(sa + 16), 0, 0);
-                    const uint32_t wv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                    const uint4 v0 = load16(pr, (uint32_t)sa), v1 = load16(pr, (uint32_t)(sa + 16));
+                    const uint32_t wv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
                     const uint32_t d = sft >> 2, s = sft & 3u;
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
@@ -338,8 +327,8 @@ tx_build(TxArgs a)
                 bool full = true;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    const uint32_t hm = win_mask(-r0c, hq - r0c, t);
-                    const uint32_t pm = win_mask(hq - r0c, hq + (int)Lq - r0c, t);
+                    const uint32_t hm = dword_window(-r0c, hq - r0c, t);
+                    const uint32_t pm = dword_window(hq - r0c, hq + (int)Lq - r0c, t);
                     o[t] = (H[t] & hm) | (P[t] & pm);
                     own[t] = hm | pm;
                     full = full && own[t] == 0xFFFFFFFFu;
