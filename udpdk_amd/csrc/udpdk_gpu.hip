@@ -118,6 +118,8 @@ struct udpdk_gpu_ctx {
     bool no_span = false;          // UDPDK_RX_SPAN=0 (tests, A/B): no span sweep (RxArgs::span)
     int policy = 1;                // UDPDK_RX_POLICY=0 (tests, A/B): rx_classify<.., 0>, default memory policy
     bool trace = false;            // UDPDK_RX_TRACE (diagnostic): the form of every call on stderr
+    uint32_t scan_cols_tiles = SCAN_COLS_MAX_TILES;   // UDPDK_RX_SCAN_COLS_TILES (tests): most tiles of the
+                                                      // one-launch column scan, 0 = always reduce / top / down
     bool no_inline = false;        // UDPDK_RX_NO_INLINE (tests, A/B): always the port-table loads
     uint32_t scatter_group_frames = UDPDK_SCATTER_GROUP_FRAMES;   // UDPDK_SCATTER_GROUP_FRAMES (tests, A/B)
     uint32_t scatter_min_wg = UDPDK_SCATTER_MIN_WG;               // UDPDK_SCATTER_MIN_WG (tests, A/B)
@@ -322,6 +324,8 @@ int udpdk_gpu_ctx_create(int device, uint32_t max_frames, uint32_t max_lanes, ud
     if (const char *e = getenv("UDPDK_RX_FUSE")) c->force_fuse = atoi(e) ? 1 : 0;
     c->trace = getenv("UDPDK_RX_TRACE") != nullptr;
     c->no_inline = getenv("UDPDK_RX_NO_INLINE") != nullptr;
+    if (const char *e = getenv("UDPDK_RX_SCAN_COLS_TILES"))
+        c->scan_cols_tiles = (uint32_t)std::min<long>(std::max<long>(atol(e), 0), (long)SCAN_COLS_MAX_TILES);
     if (const char *e = getenv("UDPDK_RX_MR")) c->force_mr = atoi(e) ? 1 : 0;
     if (const char *e = getenv("UDPDK_RX_SPAN")) c->no_span = atoi(e) == 0;
     if (const char *e = getenv("UDPDK_RX_POLICY")) c->policy = atoi(e) ? 1 : 0;
@@ -675,7 +679,9 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
 
     // the one-launch column scan while each thread's tile chunk fits its registers; beyond (very
     // large batches over few lanes) the reduce / top / down chain over u32 counts
-    const bool cols = !one_lane && tiles <= SCAN_COLS_MAX_TILES;
+    // (UDPDK_RX_SCAN_COLS_TILES lowers the bound: the chain then rescans P.hist in place and the
+    // scatter reads its rows there, row G s for a scatter tile of G classify tiles, as past the bound)
+    const bool cols = !one_lane && tiles <= c->scan_cols_tiles;
     // u16 tile histograms where a lane's count per tile cannot pass 2^16 (no fan-out): half the
     // bytes classify stores at its tile ends and the scan reads
     const bool hist16 = cols && c->max_fanout <= 1;
@@ -740,14 +746,24 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
     // each next round's descriptors a round ahead
     const bool mr = c->force_mr >= 0 ? c->force_mr == 1 : T > (uint32_t)RX_ROUND;
     auto cls = classify_form(tailg, mr ? 1 : 0, c->policy);
+    // UDPDK_RX_TRACE, second line: the geometry and the launches this call takes after classify
+    auto trace_form = [&](const char *scan, const char *scatter, uint32_t g) {
+        if (c->trace)
+            fprintf(stderr, "udpdk_gpu_rx seq %u form T %u tiles %u mr %d hist16 %d scan %s scatter %s G %u\n",
+                    seq, T, tiles, mr ? 1 : 0, hist16 ? 1 : 0, scan, scatter, g);
+    };
     // the span sweep: the long-frame form of one-round tiles (its LDS ring after the carve)
     const uint32_t cls_lds = classify_lds_bytes(S, T, hist16);
     ra.span = tailg == 2 && !mr && T == (uint32_t)RX_ROUND && !c->no_span &&
               cls_lds + SPAN_LDS_BYTES <= 160u * 1024u - 1024u ? 1u : 0u;
     HIPC(c, launch(st, ts, 0, true, true, cls, dim3(tiles),
                    dim3(CLS_BLOCK), cls_lds + (ra.span ? SPAN_LDS_BYTES : 0u), ra));
-    if (fuse) return 0;                        // the last workgroup completed the lane
+    if (fuse) {                                // the last workgroup completed the lane
+        trace_form("none", "fused", 1u);
+        return 0;
+    }
     if (one_lane) {
+        trace_form("none", "compact1", 1u);
         Compact1Args ca;
         ca.meta = o->meta_dev;
         ca.tile_count = P.hist;
@@ -812,6 +828,7 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
     sa.ticket = P.ticket;
     sa.epoch = ++P.epoch ? P.epoch : ++P.epoch;        // 0 marks a never-written look-back word
     sa.hist16 = ra.hist16;
+    const char *scan_kind = "3pass";
     if (cols) {
         // lanes per workgroup: as many as the chunking allows (<= 64, 256 B rows), then fewer
         // until the grid has >= UDPDK_SCAN_MIN_WG workgroups, never under 8 lanes (32 B row
@@ -828,6 +845,7 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
             return lb;
         };
         const uint32_t lb1 = pick_lb(1024u);
+        scan_kind = lb1 >= 4 ? "cols1024" : "cols512";
         if (lb1 >= 4) {
             HIPC(c, launch(st, ts, 1, true, true, rx_scan_cols<1024>, dim3(ceil_div(S, 1u << lb1)),
                            dim3(1024), 0u, sa, lb1));
@@ -863,6 +881,8 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
     xa.lane_cap = o->lane_cap;
     xa.row_step = 1;
     xa.dbg = c->dbg;
+    trace_form(scan_kind, !scatterw ? "scatter1" : W == SCATTER_WAVES ? "scatterw8" : "scatterw16", G);
+    static_assert(SCATTER_WAVES == 8, "the trace line names rx_scatterw's forms by their waves");
     if (scatterw) {
         xa.tile_frames = G * T;
         xa.n_tiles = ceil_div(tiles, G);
