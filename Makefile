@@ -15,9 +15,9 @@ C_SRC     := $(wildcard udpdk_amd/csrc/host/*.c)
 HIP_OBJ   := $(patsubst udpdk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
 C_OBJ     := $(patsubst udpdk_amd/csrc/host/%.c,$(OBJDIR)/host/%.o,$(C_SRC))
 HDRS      := include/udpdk_gpu.h include/udpdk_api.h udpdk_amd/csrc/rx_common.h \
-             udpdk_amd/csrc/wave.h udpdk_amd/csrc/stamps.h $(wildcard udpdk_amd/csrc/host/*.h)
+             udpdk_amd/csrc/rx_plan.h udpdk_amd/csrc/wave.h udpdk_amd/csrc/stamps.h $(wildcard udpdk_amd/csrc/host/*.h)
 
-TOOLS     := tools/bin/bench_sock
+TOOLS     := tools/bin/bench_sock build/rx_plan_check
 
 all: $(LIB) oracle $(TOOLS)
 
@@ -40,6 +40,12 @@ oracle: $(LIB)
 tools/bin/bench_sock: tools/bench_sock.c include/udpdk_api.h include/udpdk_gpu.h $(LIB)
 	@mkdir -p tools/bin
 	$(CC) -O2 -std=gnu11 -Wall -Wextra -Werror -Iinclude $< -o $@ -Ludpdk_amd -ludpdk_amd -Wl,-rpath,'$$ORIGIN/../../udpdk_amd'
+
+# the RX launch planner behind a main(): host code only, links no project library and runs on a
+# machine without a GPU (tests/test_rx_plan.py)
+build/rx_plan_check: tools/rx_plan_check.cpp $(HDRS)
+	@mkdir -p build
+	$(HIPCC) -x hip --cuda-host-only -O1 -std=c++17 -Wall -Werror $(INC) $< -o $@
 
 # diagnostic library with per-phase s_memtime stamps (tools/stamps.py); never used by tests/bench
 STAMP_LIB := tools/diag/libudpdk_amd.so

@@ -35,7 +35,7 @@ ENV = ("UDPDK_RX_TAILG", "UDPDK_RX_MR", "UDPDK_RX_POLICY", "UDPDK_RX_SCAN_COLS_T
 
 
 def _geom(n, lanes, cap=HIST_CAP):
-    """udpdk_gpu.hip's geometry(): (frames per tile, tiles)."""
+    """rx_plan.h's geometry(): (frames per tile, tiles)."""
     t = 1024
     while t < 8192 and -(-n // t) * lanes > cap:
         t *= 2

@@ -18,6 +18,7 @@
 
 #include "udpdk_gpu.h"
 #include "rx_common.h"
+#include "rx_plan.h"
 
 using namespace udpdk;
 
@@ -104,28 +105,13 @@ struct udpdk_gpu_ctx {
     // the bound ports when there are at most UDPDK_INLINE_PORTS (RxArgs::inl)
     uint32_t inl = 0, n_inl = 0, inl_port[UDPDK_INLINE_PORTS] = {};
     uint4 inl_ent[UDPDK_INLINE_PORTS] = {};
-    uint32_t one_lane_tile = 0;    // UDPDK_ONE_LANE_TILE (diagnostic): single-lane tile override
-    uint64_t geo_cap = RX_HIST_CAP; // UDPDK_RX_HIST_CAP (diagnostic): lanes x tiles bound of the geometry
+    RxKnobs knobs;                 // the environment knobs, parsed once at creation (rx_plan.h)
     // Kernel hints (pinned host memory the kernels write, RxArgs::hint): the call sequence number
     // of the last call that ran a tail pass / had a tile before the last not full. The single-lane
     // path takes rx_classify<1> and the fused completion while neither was seen in the last
     // UDPDK_HINT_WINDOW calls; both forms are exact for any batch, the hint only picks the faster.
     uint32_t *hint = nullptr;
     uint32_t rx_seq = 0;
-    int force_fuse = -1;           // UDPDK_RX_FUSE=0/1 (tests, A/B): fused completion off / always
-    int force_tailg = 0;           // UDPDK_RX_TAILG=1/2 (tests, A/B): rx_classify<G> always
-    int force_mr = -1;             // UDPDK_RX_MR=0/1 (tests, A/B): the round-ahead descriptor form
-    bool no_span = false;          // UDPDK_RX_SPAN=0 (tests, A/B): no span sweep (RxArgs::span)
-    int policy = 1;                // UDPDK_RX_POLICY=0 (tests, A/B): rx_classify<.., 0>, default memory policy
-    bool trace = false;            // UDPDK_RX_TRACE (diagnostic): the form of every call on stderr
-    uint32_t scan_cols_tiles = SCAN_COLS_MAX_TILES;   // UDPDK_RX_SCAN_COLS_TILES (tests): most tiles of the
-                                                      // one-launch column scan, 0 = always reduce / top / down
-    bool no_inline = false;        // UDPDK_RX_NO_INLINE (tests, A/B): always the port-table loads
-    uint32_t scatter_group_frames = UDPDK_SCATTER_GROUP_FRAMES;   // UDPDK_SCATTER_GROUP_FRAMES (tests, A/B)
-    uint32_t scatter_min_wg = UDPDK_SCATTER_MIN_WG;               // UDPDK_SCATTER_MIN_WG (tests, A/B)
-    uint32_t tx_parts = 0;         // UDPDK_TX_PARTS=1..4 (tests): TxArgs::parts, 0 = computed per batch
-    uint32_t tx_grid = 4096;       // UDPDK_TX_GRID>=1 (tests): tx_build's workgroup cap
-    uint32_t gather_grid = 16384;  // UDPDK_GATHER_GRID>=1 (tests): rx_gather's workgroup cap
     bool have_snapshot = false;
 
     // RX workspace, one set per pipe
@@ -133,9 +119,7 @@ struct udpdk_gpu_ctx {
     int depth = 1;                            // udpdk_gpu_pipeline_depth
     uint64_t rx_calls = 0;
     int last_pipe = -1;                       // pipe of the last udpdk_gpu_rx (-1: none yet)
-    size_t hist_cap = 0;
-    size_t partial_cap = 0;
-    size_t tiles_cap = 0;
+    RxCaps caps{};                            // entries of each pipe's hist / partial / tile_cnt
 
     uint64_t host_calls = 0;                  // udpdk_gpu_rx_host_async calls (pipe choice)
 
@@ -171,8 +155,6 @@ struct udpdk_gpu_ctx {
 
 namespace {
 
-uint32_t ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
-
 // Range of the frames buffer resource. Buffer loads are range-checked per dword (a dword is
 // returned only if it ends within the range, zero otherwise, with no memory access:
 // tools/probe/range_probe.hip) and the RX kernels load at byte-aligned frame offsets, so a
@@ -182,14 +164,6 @@ uint32_t ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); 
 uint32_t frames_rsrc_bytes(uint64_t frames_bytes)
 {
     return (uint32_t)std::min<uint64_t>((frames_bytes + 3 + 3) & ~3ull, 0xFFFFFFFCull);
-}
-
-void geometry(uint32_t n, uint32_t lanes, uint32_t *T, uint32_t *tiles, uint64_t cap = RX_HIST_CAP)
-{
-    uint32_t t = RX_TILE_MIN;
-    while (t < RX_TILE_MAX && (uint64_t)ceil_div(n, t) * lanes > cap) t *= 2;
-    *T = t;
-    *tiles = std::max<uint32_t>(1u, ceil_div(n, t));
 }
 
 int fold_timing(udpdk_gpu_ctx *c)
@@ -234,6 +208,32 @@ hipError_t launch(hipStream_t st, TimingSet *ts, int k, bool first, bool last, K
         hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
     }
     return hipGetLastError();
+}
+
+// One kernel of a single-launch call (rx_gather, tx_build); with timing on, between two events
+// the call waits for, its time added to kernel `kid`.
+template <typename K, typename A>
+int launch_timed(udpdk_gpu_ctx *c, hipStream_t st, int kid, K kern, dim3 grid, dim3 block, const A &args)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c->timing_every) {
+        HIPC(c, hipEventCreate(&e0));
+        HIPC(c, hipEventCreate(&e1));
+        HIPC(c, hipEventRecord(e0, st));
+    }
+    hipLaunchKernelGGL(kern, grid, block, 0, st, args);
+    HIPC(c, hipGetLastError());
+    if (c->timing_every) {
+        HIPC(c, hipEventRecord(e1, st));
+        HIPC(c, hipEventSynchronize(e1));
+        float ms = 0;
+        HIPC(c, hipEventElapsedTime(&ms, e0, e1));
+        c->ms[kid] += ms;
+        c->launches[kid]++;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    return 0;
 }
 
 // Order everything enqueued on the other pipes before what comes next on the context stream.
@@ -313,32 +313,8 @@ int udpdk_gpu_ctx_create(int device, uint32_t max_frames, uint32_t max_lanes, ud
     c->device = device;
     c->max_frames = max_frames;
     c->max_lanes = max_lanes;
-    if (const char *e = getenv("UDPDK_ONE_LANE_TILE")) {
-        const uint32_t t = (uint32_t)atoi(e);
-        if (t >= RX_TILE_MIN && t <= RX_TILE_MAX && (t & (t - 1)) == 0) c->one_lane_tile = t;
-    }
-    if (const char *e = getenv("UDPDK_RX_HIST_CAP")) {
-        const uint64_t v = strtoull(e, nullptr, 0);
-        if (v >= (1u << 16) && v <= (1u << 26)) c->geo_cap = v;
-    }
-    if (const char *e = getenv("UDPDK_RX_FUSE")) c->force_fuse = atoi(e) ? 1 : 0;
-    c->trace = getenv("UDPDK_RX_TRACE") != nullptr;
-    c->no_inline = getenv("UDPDK_RX_NO_INLINE") != nullptr;
-    if (const char *e = getenv("UDPDK_RX_SCAN_COLS_TILES"))
-        c->scan_cols_tiles = (uint32_t)std::min<long>(std::max<long>(atol(e), 0), (long)SCAN_COLS_MAX_TILES);
-    if (const char *e = getenv("UDPDK_RX_MR")) c->force_mr = atoi(e) ? 1 : 0;
-    if (const char *e = getenv("UDPDK_RX_SPAN")) c->no_span = atoi(e) == 0;
-    if (const char *e = getenv("UDPDK_RX_POLICY")) c->policy = atoi(e) ? 1 : 0;
-    if (const char *e = getenv("UDPDK_SCATTER_GROUP_FRAMES")) c->scatter_group_frames = (uint32_t)atoi(e);
-    if (const char *e = getenv("UDPDK_SCATTER_MIN_WG")) c->scatter_min_wg = (uint32_t)atoi(e);
-    if (const char *e = getenv("UDPDK_RX_TAILG")) {
-        const int g = atoi(e);
-        if (g == 1 || g == 2) c->force_tailg = g;
-    }
-    // (out-of-range values are clamped)
-    if (const char *e = getenv("UDPDK_TX_PARTS")) c->tx_parts = (uint32_t)std::min(std::max(atoi(e), 1), 4);
-    if (const char *e = getenv("UDPDK_TX_GRID")) c->tx_grid = (uint32_t)std::max(atoi(e), 1);
-    if (const char *e = getenv("UDPDK_GATHER_GRID")) c->gather_grid = (uint32_t)std::max(atoi(e), 1);
+    c->knobs = rx_knobs_from_env();
+    c->caps = rx_caps(max_frames, max_lanes, c->knobs.geo_cap);
     int rc = -EIO;
     do {
         if (hipSetDevice(device) != hipSuccess) break;
@@ -351,22 +327,17 @@ int udpdk_gpu_ctx_create(int device, uint32_t max_frames, uint32_t max_lanes, ud
         c->stream = c->pipes[0].stream;
         if (hipMalloc((void **)&c->port_tab, UDPDK_UDP_PORTS * sizeof(uint4)) != hipSuccess) break;
         if (hipMemset(c->port_tab, 0, UDPDK_UDP_PORTS * sizeof(uint4)) != hipSuccess) break;
-        const uint64_t e_cap = std::max<uint64_t>(std::max<uint64_t>(RX_HIST_CAP, c->geo_cap) + max_lanes,
-                                                  (uint64_t)ceil_div(max_frames, RX_TILE_MAX) * max_lanes);
-        c->hist_cap = e_cap;
-        c->partial_cap = e_cap / SCAN_COL_CHUNK + max_lanes + 1;   // chunks x lanes
-        c->tiles_cap = ceil_div(max_frames, RX_TILE_MIN) + 1;
         for (Pipe &P : c->pipes) {
-            ok = ok && hipMalloc((void **)&P.hist, e_cap * 4) == hipSuccess;
-            ok = ok && hipMalloc((void **)&P.partial, c->partial_cap * 4) == hipSuccess;
-            ok = ok && hipMalloc((void **)&P.base, e_cap * 4) == hipSuccess;
+            ok = ok && hipMalloc((void **)&P.hist, c->caps.hist_cap * 4) == hipSuccess;
+            ok = ok && hipMalloc((void **)&P.partial, c->caps.partial_cap * 4) == hipSuccess;
+            ok = ok && hipMalloc((void **)&P.base, c->caps.hist_cap * 4) == hipSuccess;
             // one look-back word per lane block: down to one lane per block when a batch has so
             // many tiles that a column chunk holds a single lane (rx_scan_cols' lb = 0)
             ok = ok && hipMalloc((void **)&P.agg, ((size_t)max_lanes + 1) * 8) == hipSuccess;
             ok = ok && hipMemset(P.agg, 0, ((size_t)max_lanes + 1) * 8) == hipSuccess;
             ok = ok && hipMalloc((void **)&P.ticket, 64) == hipSuccess;
             ok = ok && hipMemset(P.ticket, 0, 64) == hipSuccess;
-            ok = ok && hipMalloc((void **)&P.tile_cnt, c->tiles_cap * UDPDK_N_COUNTERS * 4) == hipSuccess;
+            ok = ok && hipMalloc((void **)&P.tile_cnt, c->caps.tiles_cap * UDPDK_N_COUNTERS * 4) == hipSuccess;
             ok = ok && hipMalloc((void **)&P.res, sizeof(DevResult)) == hipSuccess;
             ok = ok && hipMemset(P.res, 0, sizeof(DevResult)) == hipSuccess;
             ok = ok && hipHostMalloc((void **)&P.h_res, sizeof(DevResult), hipHostMallocDefault) == hipSuccess;
@@ -390,7 +361,7 @@ int udpdk_gpu_ctx_create(int device, uint32_t max_frames, uint32_t max_lanes, ud
             160u * 1024u - 1024u);   // static LDS besides
         for (int g = 1; g <= 2 && ok; ++g)
             for (int mr = 0; mr <= 1 && ok; ++mr)
-                ok = hipFuncSetAttribute((const void *)classify_form(g, mr, c->policy),
+                ok = hipFuncSetAttribute((const void *)classify_form(g, mr, c->knobs.policy),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, cls_lds) == hipSuccess;
         if (!ok) break;
         if (hipFuncSetAttribute((const void *)rx_scatter, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -597,7 +568,7 @@ int udpdk_gpu_bind_snapshot_upload(udpdk_gpu_ctx *c, const udpdk_bind_snapshot_t
     while ((1u << kb) < s->n_lanes) ++kb;
     c->key_bits = kb;
     c->max_fanout = maxfan;
-    c->inl = nports <= UDPDK_INLINE_PORTS && !c->no_inline ? 1u : 0u;
+    c->inl = nports <= UDPDK_INLINE_PORTS && !c->knobs.no_inline ? 1u : 0u;
     c->n_inl = c->inl ? nports : 0u;
     for (uint32_t k = 0; k < UDPDK_INLINE_PORTS; ++k) {
         c->inl_port[k] = iport[k];
@@ -665,29 +636,27 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
         if (ts) c->n_sets_used--;                         // nothing was launched
         return 0;
     }
-    uint32_t T, tiles;
-    geometry(bt->n, S, &T, &tiles, c->geo_cap);
-    if (S == 1 && c->max_fanout <= 1 && c->one_lane_tile) {   // diagnostic override
-        T = c->one_lane_tile;
-        tiles = std::max<uint32_t>(1u, ceil_div(bt->n, T));
+    // the kernel form from the hints of the recent calls (RxArgs::hint), measured against the
+    // latest call the GPU has reached (the host may run tens of calls ahead)
+    const uint32_t done = __atomic_load_n(&c->hint[UDPDK_HINT_DONE], __ATOMIC_RELAXED);
+    const uint32_t tail = __atomic_load_n(&c->hint[UDPDK_HINT_TAIL], __ATOMIC_RELAXED);
+    const bool tail_recent = tail != 0u && (int32_t)(done - tail) <= (int32_t)UDPDK_HINT_WINDOW;
+    const RxPlan p = rx_plan(bt->n, S, c->max_fanout, tail_recent, c->knobs, c->caps);
+    if (p.err) return p.err;
+    P.last_tiles = p.tiles;
+    if (p.spec && ++P.spec_epoch == 0) P.spec_epoch = 1;       // 0: the zeroed word's tag
+    if (++c->rx_seq == 0) c->rx_seq = 1;
+    const uint32_t seq = c->rx_seq;
+    if (c->knobs.trace) {                      // UDPDK_RX_TRACE: the classify form, then the geometry
+        char cls[32], form[128];               // and the launches this call takes after classify
+        rx_plan_trace(p, cls, form);
+        fprintf(stderr, "udpdk_gpu_rx seq %u done %u hint tail %u nonfull %u -> %s\nudpdk_gpu_rx seq %u form %s\n",
+                seq, done, tail, c->hint[UDPDK_HINT_NONFULL], cls, seq, form);
     }
-    const uint64_t E = (uint64_t)S * tiles;
-    if (E > c->hist_cap || tiles > c->tiles_cap) return -EINVAL;
-    // single lane, no fan-out: classify + rx_compact1; otherwise classify + scan + scatter
-    const bool one_lane = S == 1 && c->max_fanout <= 1;
-    P.last_tiles = tiles;
 
-    // the one-launch column scan while each thread's tile chunk fits its registers; beyond (very
-    // large batches over few lanes) the reduce / top / down chain over u32 counts
-    // (UDPDK_RX_SCAN_COLS_TILES lowers the bound: the chain then rescans P.hist in place and the
-    // scatter reads its rows there, row G s for a scatter tile of G classify tiles, as past the bound)
-    const bool cols = !one_lane && tiles <= c->scan_cols_tiles;
-    // u16 tile histograms where a lane's count per tile cannot pass 2^16 (no fan-out): half the
-    // bytes classify stores at its tile ends and the scan reads
-    const bool hist16 = cols && c->max_fanout <= 1;
     RxArgs ra;
     memset(&ra, 0, sizeof(ra));
-    ra.hist16 = hist16 ? 1u : 0u;
+    ra.hist16 = p.hist16 ? 1u : 0u;
     ra.frames = bt->frames_dev;
     ra.offset = bt->offset_dev;
     ra.length = bt->length_dev;
@@ -702,8 +671,8 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
     ra.frames_bytes = (uint32_t)bt->frames_bytes;
     ra.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
     ra.n = bt->n;
-    ra.tile_frames = T;
-    ra.n_tiles = tiles;
+    ra.tile_frames = p.T;
+    ra.n_tiles = p.tiles;
     ra.lane_mask = c->lane_mask;
     ra.n_lanes = S;
     ra.inl = c->inl;
@@ -712,58 +681,22 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
         ra.inl_port[k] = c->inl_port[k];
         ra.inl_ent[k] = c->inl_ent[k];
     }
-    // speculative single-lane entries from classify (see RxArgs::spec_pkt)
-    const bool spec = UDPDK_SPEC_COMPACT && one_lane && T == (uint32_t)RX_ROUND && CLS_BLOCK * 4 == RX_ROUND;
-    ra.spec_pkt = spec ? o->lane_pkt_dev : nullptr;
-    ra.spec_cap = spec ? o->lane_cap : 0u;
-    if (spec && ++P.spec_epoch == 0) P.spec_epoch = 1;       // 0: the zeroed word's tag
-    ra.spec_nonfull = spec ? P.res->nonfull : nullptr;
+    ra.spec_pkt = p.spec ? o->lane_pkt_dev : nullptr;          // see RxArgs::spec_pkt
+    ra.spec_cap = p.spec ? o->lane_cap : 0u;
+    ra.spec_nonfull = p.spec ? P.res->nonfull : nullptr;
     ra.spec_epoch = P.spec_epoch;
-    // kernel form from the hints of the recent calls (RxArgs::hint)
-    if (++c->rx_seq == 0) c->rx_seq = 1;
-    const uint32_t seq = c->rx_seq;
-    // measured against the latest call the GPU has reached (the host may run tens of calls ahead)
-    const uint32_t done = __atomic_load_n(&c->hint[UDPDK_HINT_DONE], __ATOMIC_RELAXED);
-    auto recent = [&](int k) {
-        const uint32_t v = __atomic_load_n(&c->hint[k], __ATOMIC_RELAXED);
-        return v != 0u && (int32_t)(done - v) <= (int32_t)UDPDK_HINT_WINDOW;
-    };
     ra.hint = c->hint;
     ra.seq = seq;
-    // fused completion whenever it applies: a call with a short tile repairs its lane inside the
-    // same launch (classify_complete), so no form switching follows a stray frame
-    const bool fuse = spec && tiles <= UDPDK_FUSE_MAX_TILES && c->force_fuse != 0;
-    const int tailg = c->force_tailg ? c->force_tailg : (one_lane && !recent(UDPDK_HINT_TAIL)) ? 1 : 2;
-    if (c->trace)
-        fprintf(stderr, "udpdk_gpu_rx seq %u done %u hint tail %u nonfull %u -> classify<%d>%s\n", seq,
-                done, c->hint[UDPDK_HINT_TAIL], c->hint[UDPDK_HINT_NONFULL], tailg, fuse ? " fused" : "");
-    ra.fuse = fuse ? P.fuse : nullptr;
+    ra.fuse = p.fuse ? P.fuse : nullptr;
     ra.lane_off = o->lane_off_dev;
     ra.total = &P.res->total;
+    ra.span = p.span ? 1u : 0u;
 
     if (ts) for (int k = 0; k < TIMED_KERNELS; ++k) ts->used[k] = false;
-    // tiles of several rounds (many lanes: config 5's 8192-frame tiles) take the form that loads
-    // each next round's descriptors a round ahead
-    const bool mr = c->force_mr >= 0 ? c->force_mr == 1 : T > (uint32_t)RX_ROUND;
-    auto cls = classify_form(tailg, mr ? 1 : 0, c->policy);
-    // UDPDK_RX_TRACE, second line: the geometry and the launches this call takes after classify
-    auto trace_form = [&](const char *scan, const char *scatter, uint32_t g) {
-        if (c->trace)
-            fprintf(stderr, "udpdk_gpu_rx seq %u form T %u tiles %u mr %d hist16 %d scan %s scatter %s G %u\n",
-                    seq, T, tiles, mr ? 1 : 0, hist16 ? 1 : 0, scan, scatter, g);
-    };
-    // the span sweep: the long-frame form of one-round tiles (its LDS ring after the carve)
-    const uint32_t cls_lds = classify_lds_bytes(S, T, hist16);
-    ra.span = tailg == 2 && !mr && T == (uint32_t)RX_ROUND && !c->no_span &&
-              cls_lds + SPAN_LDS_BYTES <= 160u * 1024u - 1024u ? 1u : 0u;
-    HIPC(c, launch(st, ts, 0, true, true, cls, dim3(tiles),
-                   dim3(CLS_BLOCK), cls_lds + (ra.span ? SPAN_LDS_BYTES : 0u), ra));
-    if (fuse) {                                // the last workgroup completed the lane
-        trace_form("none", "fused", 1u);
-        return 0;
-    }
-    if (one_lane) {
-        trace_form("none", "compact1", 1u);
+    HIPC(c, launch(st, ts, 0, true, true, classify_form(p.tailg, p.mr ? 1 : 0, c->knobs.policy), dim3(p.tiles),
+                   dim3(CLS_BLOCK), p.cls_lds, ra));
+    if (p.fuse) return 0;                      // the last workgroup completed the lane
+    if (p.one_lane) {
         Compact1Args ca;
         ca.meta = o->meta_dev;
         ca.tile_count = P.hist;
@@ -771,101 +704,54 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
         ca.lane_off = o->lane_off_dev;
         ca.total = &P.res->total;
         ca.n = bt->n;
-        ca.tile_frames = T;
-        ca.n_tiles = tiles;
+        ca.tile_frames = p.T;
+        ca.n_tiles = p.tiles;
         ca.lane_cap = o->lane_cap;
-        ca.base = nullptr;
-        ca.spec = spec ? 1u : 0u;
+        ca.base = p.tile_base ? P.partial : nullptr;
+        ca.spec = p.spec ? 1u : 0u;
         ca.spec_nonfull = P.res->nonfull;
         ca.spec_epoch = P.spec_epoch;
         ca.hint = c->hint;
         ca.seq = seq;
-        if (tiles > COMPACT1_DIRECT_TILES && tiles <= c->partial_cap) {
-            // past a few thousand tiles each workgroup's sum over its predecessors costs more
-            // than one extra launch scanning the counts once
+        if (p.tile_base) {
             hipLaunchKernelGGL(rx_tile_base, dim3(1), dim3(1024), 0, st, (const uint32_t *)P.hist,
-                               P.partial, tiles);
+                               P.partial, p.tiles);
             HIPC(c, hipGetLastError());
-            ca.base = P.partial;
         }
-        // speculative: grid-stride over the tiles after the call's first flagged one (usually
-        // none); the grid size does not change the all-full call's cost (same-box A/B: 32, 128
-        // and 1024 workgroups all 4.8-5.0 us), 256 keeps a flagged call's rewrite wide
-        const uint32_t cgrid = spec ? std::min<uint32_t>(tiles, UDPDK_COMPACT1_SPEC_GRID) : tiles;
-        HIPC(c, launch(st, ts, 2, true, true, rx_compact1, dim3(cgrid), dim3(RX_BLOCK), 0u, ca));
+        HIPC(c, launch(st, ts, 2, true, true, rx_compact1, dim3(p.compact_grid), dim3(RX_BLOCK), 0u, ca));
         return 0;
-    }
-
-    // rx_scatterw: G classify tiles per scatter workgroup while the scatter tile stays within
-    // UDPDK_SCATTER_GROUP_FRAMES, its (frame, position) pairs fit the LDS counter region (8 B each
-    // in 2 W S bytes) and the grid keeps UDPDK_SCATTER_MIN_WG workgroups; the column scan then
-    // writes only the base rows of each group's first tile
-    const bool scatterw = c->max_fanout <= 1 && S <= SCATTERW_MAX_LANES;
-    uint32_t G = 1, W = SCATTER_WAVES;
-    while (scatterw && G < tiles) {
-        const uint32_t g2 = 2 * G, f2 = g2 * T;
-        const uint32_t w2 = f2 > 64u * SCATTER_WAVES * SCATTERW_MV ? 2 * SCATTER_WAVES : SCATTER_WAVES;
-        if (f2 > c->scatter_group_frames || f2 > 64u * w2 * SCATTERW_MV || 8ull * f2 > 2ull * w2 * S ||
-            (S & 1u) || ceil_div(tiles, g2) < c->scatter_min_wg)
-            break;
-        G = g2;
-        W = w2;
     }
 
     ScanArgs sa;
     memset(&sa, 0, sizeof(sa));
-    sa.row_mask = cols ? G - 1u : 0u;
+    sa.row_mask = p.cols ? p.G - 1u : 0u;
     sa.dbg = c->dbg;
     sa.hist = P.hist;
     sa.partial = P.partial;
     sa.lane_off = o->lane_off_dev;
     sa.total = &P.res->total;
-    sa.n_elems = (uint32_t)E;
-    sa.n_tiles = tiles;
+    sa.n_elems = S * p.tiles;
+    sa.n_tiles = p.tiles;
     sa.n_lanes = S;
     sa.base = P.base;
     sa.agg = P.agg;
     sa.ticket = P.ticket;
     sa.epoch = ++P.epoch ? P.epoch : ++P.epoch;        // 0 marks a never-written look-back word
     sa.hist16 = ra.hist16;
-    const char *scan_kind = "3pass";
-    if (cols) {
-        // lanes per workgroup: as many as the chunking allows (<= 64, 256 B rows), then fewer
-        // until the grid has >= UDPDK_SCAN_MIN_WG workgroups, never under 8 lanes (32 B row
-        // segments). Wider rows beat more workgroups: at 1024 lanes x 1024 tiles, 16-lane
-        // columns (64 workgroups) take 8.0 us, 8-lane (128) 11.9 us, 4-lane (256) 13.0 us.
-        // Workgroups of 1024 threads when that still leaves >= 16-lane columns (config 5: 11.2-11.8
-        // -> 7.3-7.7 us against 256 threads; more waves per CU for the column loads' latency),
-        // else 512 (config 4's 1024 lanes x 1024 tiles: 10.3-10.4 -> 8.9-9.1 us)
-        auto pick_lb = [&](uint32_t block) {
-            const uint32_t cmin = ceil_div(tiles, scan_cols_tpt(block));
-            uint32_t lb = 0;
-            while ((2u << lb) <= std::min<uint32_t>(64u, block / cmin)) ++lb;
-            while (lb > 3 && ceil_div(S, 1u << lb) < UDPDK_SCAN_MIN_WG) --lb;
-            return lb;
-        };
-        const uint32_t lb1 = pick_lb(1024u);
-        scan_kind = lb1 >= 4 ? "cols1024" : "cols512";
-        if (lb1 >= 4) {
-            HIPC(c, launch(st, ts, 1, true, true, rx_scan_cols<1024>, dim3(ceil_div(S, 1u << lb1)),
-                           dim3(1024), 0u, sa, lb1));
-        } else {
-            const uint32_t lb = pick_lb(512u);
-            HIPC(c, launch(st, ts, 1, true, true, rx_scan_cols<512>, dim3(ceil_div(S, 1u << lb)),
-                           dim3(512), 0u, sa, lb));
-        }
+    if (p.scan != RX_SCAN_3PASS) {
+        const bool wide = p.scan == RX_SCAN_COLS1024;
+        HIPC(c, launch(st, ts, 1, true, true, wide ? rx_scan_cols<1024> : rx_scan_cols<512>, dim3(p.scan_grid),
+                       dim3(wide ? 1024 : 512), 0u, sa, p.lb));
     } else {
-        const uint32_t nc = ceil_div(tiles, SCAN_COL_CHUNK);
-        if ((uint64_t)nc * S > c->partial_cap) return -EINVAL;
-        const dim3 grid(nc, ceil_div(S, (uint32_t)SCAN_BLOCK));
+        const dim3 grid(p.nc, ceil_div(S, (uint32_t)SCAN_BLOCK));
         HIPC(c, launch(st, ts, 1, true, false, rx_scan_reduce, grid, dim3(SCAN_BLOCK), 0u, sa));
-        HIPC(c, launch(st, ts, 1, false, false, rx_scan_top, dim3(1), dim3(SCAN_TOP_BLOCK), 4u * S, sa, nc));
+        HIPC(c, launch(st, ts, 1, false, false, rx_scan_top, dim3(1), dim3(SCAN_TOP_BLOCK), 4u * S, sa, p.nc));
         HIPC(c, launch(st, ts, 1, false, true, rx_scan_down, grid, dim3(SCAN_BLOCK), 0u, sa));
     }
 
     ScatterArgs xa;
     xa.meta = o->meta_dev;
-    xa.base = cols ? P.base : P.hist;
+    xa.base = p.cols ? P.base : P.hist;
     xa.total = &P.res->total;
     xa.frames = bt->frames_dev;
     xa.offset = bt->offset_dev;
@@ -873,29 +759,21 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
     xa.binds = c->binds;
     xa.lane_pkt = o->lane_pkt_dev;
     xa.n = bt->n;
-    xa.tile_frames = T;
-    xa.n_tiles = tiles;
+    xa.tile_frames = p.G * p.T;                // a scatter tile is G classify tiles (rx_scatter: G = 1)
+    xa.n_tiles = ceil_div(p.tiles, p.G);
     xa.n_lanes = S;
     xa.lane_mask = c->lane_mask;
     xa.key_bits = c->key_bits;
     xa.lane_cap = o->lane_cap;
-    xa.row_step = 1;
+    xa.row_step = p.G;
     xa.dbg = c->dbg;
-    trace_form(scan_kind, !scatterw ? "scatter1" : W == SCATTER_WAVES ? "scatterw8" : "scatterw16", G);
-    static_assert(SCATTER_WAVES == 8, "the trace line names rx_scatterw's forms by their waves");
-    if (scatterw) {
-        xa.tile_frames = G * T;
-        xa.n_tiles = ceil_div(tiles, G);
-        xa.row_step = G;
-        if (W == SCATTER_WAVES)
-            HIPC(c, launch(st, ts, 2, true, true, rx_scatterw<SCATTER_WAVES>, dim3(xa.n_tiles),
-                           dim3(64 * SCATTER_WAVES), scatterw_lds_bytes(S), xa));
-        else
-            HIPC(c, launch(st, ts, 2, true, true, rx_scatterw<2 * SCATTER_WAVES>, dim3(xa.n_tiles),
-                           dim3(128 * SCATTER_WAVES), scatterw_lds_bytes(S, 2 * SCATTER_WAVES), xa));
-    } else
-        HIPC(c, launch(st, ts, 2, true, true, rx_scatter, dim3(tiles), dim3(SCATTER1_BLOCK),
+    if (!p.scatterw)
+        HIPC(c, launch(st, ts, 2, true, true, rx_scatter, dim3(p.tiles), dim3(SCATTER1_BLOCK),
                        scatter1_lds_bytes(S), xa));
+    else
+        HIPC(c, launch(st, ts, 2, true, true,
+                       p.W == SCATTER_WAVES ? rx_scatterw<SCATTER_WAVES> : rx_scatterw<2 * SCATTER_WAVES>,
+                       dim3(xa.n_tiles), dim3(64 * p.W), scatterw_lds_bytes(S, p.W), xa));
     return 0;
 }
 
@@ -1140,26 +1018,8 @@ static int rx_gather_launch(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const 
     ga.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
     ga.n = bt->n;
     ga.slot_off = slot_off_dev;
-    const uint32_t grid = std::min<uint32_t>(ceil_div(count, GATHER_BLOCK), c->gather_grid);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing_every) {
-        HIPC(c, hipEventCreate(&e0));
-        HIPC(c, hipEventCreate(&e1));
-        HIPC(c, hipEventRecord(e0, gst));
-    }
-    hipLaunchKernelGGL(rx_gather, dim3(grid), dim3(GATHER_BLOCK), 0, gst, ga);
-    HIPC(c, hipGetLastError());
-    if (c->timing_every) {
-        HIPC(c, hipEventRecord(e1, gst));
-        HIPC(c, hipEventSynchronize(e1));
-        float ms = 0;
-        HIPC(c, hipEventElapsedTime(&ms, e0, e1));
-        c->ms[UDPDK_K_RX_GATHER] += ms;
-        c->launches[UDPDK_K_RX_GATHER]++;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    return 0;
+    const uint32_t grid = std::min<uint32_t>(ceil_div(count, GATHER_BLOCK), c->knobs.gather_grid);
+    return launch_timed(c, gst, UDPDK_K_RX_GATHER, rx_gather, dim3(grid), dim3(GATHER_BLOCK), ga);
 }
 
 } // namespace
@@ -1397,8 +1257,8 @@ int udpdk_gpu_frag_table_create(udpdk_gpu_ctx *c, const udpdk_frag_table_cfg_t *
     return reasm_create(&c->reasm, c->device, c->max_frames, cfg, &c->last_err);
 }
 
-int udpdk_gpu_rx_reassemble(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const uint32_t *meta_dev,
-                            uint64_t tms, udpdk_reasm_out_t *o)
+static int reassemble(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, uint64_t tms,
+                      udpdk_reasm_out_t *o, bool inplace)
 {
     if (!c || !bt || !o) return -EINVAL;
     if (!c->reasm) return -EINVAL;
@@ -1406,19 +1266,19 @@ int udpdk_gpu_rx_reassemble(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const 
     if (bt->frames_bytes >= (1ull << 32) || bt->n > c->max_frames) return -EINVAL;
     HIPC(c, hipSetDevice(c->device));
     { int r = join_pipes(c); if (r) return r; }
-    return reasm_run(c->reasm, c->stream, bt, meta_dev, tms, o, &c->last_err, false);
+    return reasm_run(c->reasm, c->stream, bt, meta_dev, tms, o, &c->last_err, inplace);
+}
+
+int udpdk_gpu_rx_reassemble(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const uint32_t *meta_dev,
+                            uint64_t tms, udpdk_reasm_out_t *o)
+{
+    return reassemble(c, bt, meta_dev, tms, o, false);
 }
 
 int udpdk_gpu_rx_reassemble_inplace(udpdk_gpu_ctx *c, udpdk_rx_batch_t *bt, const uint32_t *meta_dev,
                                     uint64_t tms, udpdk_reasm_out_t *o)
 {
-    if (!c || !bt || !o) return -EINVAL;
-    if (!c->reasm) return -EINVAL;
-    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev || !meta_dev)) return -EINVAL;
-    if (bt->frames_bytes >= (1ull << 32) || bt->n > c->max_frames) return -EINVAL;
-    HIPC(c, hipSetDevice(c->device));
-    { int r = join_pipes(c); if (r) return r; }
-    return reasm_run(c->reasm, c->stream, bt, meta_dev, tms, o, &c->last_err, true);
+    return reassemble(c, bt, meta_dev, tms, o, true);
 }
 
 uint64_t udpdk_gpu_tx_span(uint32_t len, uint32_t mtu, uint32_t *n_frames)
@@ -1480,27 +1340,9 @@ int udpdk_gpu_tx_build_mtu(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
     // waves per group of 64 datagrams: up to 4 while groups alone would leave the chip under
     // ~16 K waves (their chunk sweeps split between them)
     ta.parts = std::max<uint32_t>(1u, std::min<uint32_t>(4u, 16384u / std::max<uint32_t>(groups, 1u)));
-    if (c->tx_parts) ta.parts = c->tx_parts;
-    const uint32_t grid = std::min<uint32_t>(ceil_div(groups * ta.parts, TX_BLOCK / 64), c->tx_grid);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing_every) {
-        HIPC(c, hipEventCreate(&e0));
-        HIPC(c, hipEventCreate(&e1));
-        HIPC(c, hipEventRecord(e0, c->stream));
-    }
-    hipLaunchKernelGGL(tx_build, dim3(grid), dim3(TX_BLOCK), 0, c->stream, ta);
-    HIPC(c, hipGetLastError());
-    if (c->timing_every) {
-        HIPC(c, hipEventRecord(e1, c->stream));
-        HIPC(c, hipEventSynchronize(e1));
-        float ms = 0;
-        HIPC(c, hipEventElapsedTime(&ms, e0, e1));
-        c->ms[UDPDK_K_TX_BUILD] += ms;
-        c->launches[UDPDK_K_TX_BUILD]++;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    return 0;
+    if (c->knobs.tx_parts) ta.parts = c->knobs.tx_parts;
+    const uint32_t grid = std::min<uint32_t>(ceil_div(groups * ta.parts, TX_BLOCK / 64), c->knobs.tx_grid);
+    return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build, dim3(grid), dim3(TX_BLOCK), ta);
 }
 
 #ifdef UDPDK_STAMPS
