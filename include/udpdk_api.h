@@ -172,6 +172,12 @@ int udpdk_config_set(const uint8_t src_mac[6], const uint8_t dst_mac[6], uint32_
 int udpdk_config_get(uint8_t src_mac[6], uint8_t dst_mac[6], uint32_t *src_ip_raw);
 /* IPv4 MTU of the TX fragmentation (default IPV4_MTU_DEFAULT = 1500; (mtu - 20) % 8 == 0). */
 int udpdk_config_mtu(uint32_t mtu);
+/* UDP checksum on sent datagrams (ini: [gpu] tx_udp_cksum = 0|1). 0 (default): the checksum
+ * field is 0 as the reference sends it (udpdk_syscall.c:343); 1: udpdk_tx_drain builds every
+ * datagram with its RFC 768 checksum (UDPDK_TX_UDP_CKSUM, udpdk_gpu.h), fragmented ones
+ * included. One switch for the whole library, taking effect from the next drain. Returns the
+ * setting in force before the call (0 or 1); a negative `on` only reads it; on > 1: -1, EINVAL. */
+int udpdk_config_tx_cksum(int on);
 
 /* Socket slot state (exch_slot_info, udpdk_types.h:40-47) for the GPU TX slot table. */
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots);

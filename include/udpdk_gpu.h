@@ -43,7 +43,9 @@ extern "C" {
 
 /* 2: udpdk_reasm_out_t stats grew to UDPDK_RS_N = 11 (RS_SERIAL, RS_SORTED);
  *    udpdk_gpu_rx_gather_packed; TX payloads need UDPDK_GPU_FRAMES_TAILROOM readable bytes
- * 3: udpdk_frag_table_cfg_t grew max_entries (the table's LRU limit) and flags (32 bytes) */
+ * 3: udpdk_frag_table_cfg_t grew max_entries (the table's LRU limit) and flags (32 bytes)
+ *    (still 3: udpdk_gpu_tx_build_flags / UDPDK_TX_UDP_CKSUM were added; a new symbol breaks no
+ *    caller) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -477,6 +479,22 @@ int udpdk_gpu_tx_build(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg,
 int udpdk_gpu_tx_build_mtu(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg,
                            const udpdk_tx_batch_t *batch, const udpdk_tx_out_t *out,
                            uint32_t mtu);
+/* udpdk_gpu_tx_build_mtu with options. flags == 0 is udpdk_gpu_tx_build_mtu exactly (same kernel,
+ * same launch form); bits outside the ones below give -EINVAL and write nothing.
+ *
+ * UDPDK_TX_UDP_CKSUM: every written datagram carries its RFC 768 checksum at bytes 40-41 of its
+ * first frame instead of the reference's 0 ("UDP checksum is optional", udpdk_syscall.c:343):
+ * the one's-complement sum of the pseudo-header (the source address the IPv4 header got,
+ * destination address, zero, 17, UDP length), the UDP header with a zero checksum field and the
+ * payload zero-padded to even length, complemented, 0 sent as 0xFFFF. With an MTU the checksum
+ * covers the whole datagram and is in fragment 0 only (later fragments carry no UDP header).
+ * Every other byte of every frame is what flags == 0 writes. The checksum is computed from the
+ * payload bytes the kernel already holds on their way to the frame (no extra memory traffic);
+ * one wave then builds a whole group of 64 datagrams, so UDPDK_TX_PARTS does not apply. */
+#define UDPDK_TX_UDP_CKSUM 1u
+int udpdk_gpu_tx_build_flags(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg,
+                             const udpdk_tx_batch_t *batch, const udpdk_tx_out_t *out,
+                             uint32_t mtu, uint32_t flags);
 /* Output bytes of one datagram of `len` payload bytes and its frame count (host helper). */
 uint64_t udpdk_gpu_tx_span(uint32_t len, uint32_t mtu, uint32_t *n_frames);
 

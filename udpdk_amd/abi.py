@@ -94,6 +94,7 @@ class FragTableCfg(C.Structure):
 
 
 FRAG_CKSUM_DPDK = 1       # UDPDK_FRAG_CKSUM_DPDK
+TX_UDP_CKSUM = 1          # UDPDK_TX_UDP_CKSUM
 
 
 class ReasmOut(C.Structure):
@@ -187,6 +188,8 @@ _PROTOS = {
     "udpdk_gpu_tx_build": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(TxBatch), C.POINTER(TxOut)]),
     "udpdk_gpu_tx_build_mtu": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(TxBatch),
                                          C.POINTER(TxOut), C.c_uint32]),
+    "udpdk_gpu_tx_build_flags": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(TxBatch),
+                                           C.POINTER(TxOut), C.c_uint32, C.c_uint32]),
     "udpdk_gpu_tx_span": (C.c_uint64, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "udpdk_gpu_timing_enable": (C.c_int, [_P, C.c_int]),
     "udpdk_gpu_timing_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
@@ -214,6 +217,7 @@ _PROTOS = {
     "udpdk_config_set": (C.c_int, [_P, _P, C.c_uint32]),
     "udpdk_config_get": (C.c_int, [_P, _P, C.POINTER(C.c_uint32)]),
     "udpdk_config_mtu": (C.c_int, [C.c_uint32]),
+    "udpdk_config_tx_cksum": (C.c_int, [C.c_int]),
     "udpdk_tx_pending": (C.c_uint64, []),
     "udpdk_tx_dropped": (C.c_uint64, []),
     "udpdk_rx_nobufs": (C.c_uint64, []),
@@ -701,6 +705,11 @@ class HostApi:
         s = C.create_string_buffer(src_mac, 6)
         d = C.create_string_buffer(dst_mac, 6)
         return self.L.udpdk_config_set(s, d, raw_ip(src_ip))
+
+    def config_tx_cksum(self, on: int) -> int:
+        """UDP checksum on sent datagrams (udpdk_config_tx_cksum): returns the previous setting;
+        a negative `on` only reads it."""
+        return self.L.udpdk_config_tx_cksum(int(on))
 
     def snapshot(self, compat: bool = False) -> BindSnapshot:
         snap = BindSnapshot()

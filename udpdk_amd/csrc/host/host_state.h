@@ -138,6 +138,8 @@ struct h_state {
     uint8_t  src_mac[6], dst_mac[6];
     uint32_t src_ip;
     uint32_t mtu;                /* IPV4_MTU_DEFAULT = RTE_ETHER_MTU (udpdk_constants.h:37)      */
+    uint32_t tx_udp_cksum;       /* [gpu] tx_udp_cksum / udpdk_config_tx_cksum: udpdk_tx_drain builds
+                                    with UDPDK_TX_UDP_CKSUM (0: checksum 0, udpdk_syscall.c:343) */
     udpdk_gpu_ctx *gpu;
     int      gpu_device;
     uint32_t gpu_max_frames, gpu_max_lanes;

@@ -39,6 +39,7 @@ static void h_config_defaults(void)
     g_udpdk.frag_ttl_ms = 1000;        /* MAX_FLOW_TTL = MS_PER_S */
     g_udpdk.frag_max_entries = 0;      /* NUM_FLOWS_MAX (rx_poll.c: h_frag_max_entries) */
     g_udpdk.frag_flags = 0;            /* RFC 1071 header checksum on reassembled datagrams */
+    g_udpdk.tx_udp_cksum = 0;          /* UDP checksum 0 on TX, udpdk_syscall.c:343 */
     g_udpdk.arena_bytes_max = 4ull << 30;
     g_udpdk.arena_count_max = 1024;
     g_udpdk.port_spec[0] = g_udpdk.port_peer[0] = 0;
@@ -70,6 +71,7 @@ void udpdk_host_reset(void)
     atomic_store(&g_udpdk.interrupted, 0);
     g_udpdk.snap_version = UINT64_MAX;
     g_udpdk.mtu = 1500;
+    g_udpdk.tx_udp_cksum = 0;
     pthread_mutex_unlock(&g_udpdk.lock);
 }
 
@@ -239,6 +241,11 @@ static int h_load_ini(const char *path)
             if (!strcmp(v, "dpdk")) g_udpdk.frag_flags |= UDPDK_FRAG_CKSUM_DPDK;
             else if (!strcmp(v, "rfc1071")) g_udpdk.frag_flags &= ~UDPDK_FRAG_CKSUM_DPDK;
             else { rc = -1; break; }
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "tx_udp_cksum")) {
+            /* 1: sent datagrams carry their RFC 768 checksum (UDPDK_TX_UDP_CKSUM); 0 (default):
+             * checksum 0 as the reference sends (udpdk_syscall.c:343) */
+            if (!strcmp(v, "0") || !strcmp(v, "1")) udpdk_config_tx_cksum(v[0] - '0');
+            else { rc = -1; break; }
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port")) {
             snprintf(g_udpdk.port_spec, sizeof(g_udpdk.port_spec), "%s", v);
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port_peer")) {
@@ -366,6 +373,14 @@ int udpdk_config_mtu(uint32_t mtu)
     if (mtu < 68u || mtu > 9000u || (mtu - 20u) % 8u) { errno = EINVAL; return -1; }
     g_udpdk.mtu = mtu;
     return 0;
+}
+
+int udpdk_config_tx_cksum(int on)
+{
+    const int was = (int)g_udpdk.tx_udp_cksum;
+    if (on > 1) { errno = EINVAL; return -1; }
+    if (on >= 0) g_udpdk.tx_udp_cksum = (uint32_t)on;
+    return was;
 }
 
 int udpdk_config_set(const uint8_t src_mac[6], const uint8_t dst_mac[6], uint32_t src_ip)

@@ -5,9 +5,10 @@
  * while the burst holds fewer than BURST_SIZE frames (a datagram longer than the MTU counts as
  * its fragments, :461-501), the burst flushed when it reaches BURST_SIZE, and the loop repeated
  * until the rings are empty or the caller's frame / byte limits stop it. The selected
- * datagrams' payloads go to the GPU in one pinned H2D, udpdk_gpu_tx_build_mtu builds every frame
+ * datagrams' payloads go to the GPU in one pinned H2D, udpdk_gpu_tx_build_flags builds every frame
  * (Ethernet/IPv4/UDP headers from the slot table of the uploaded bind snapshot, rte_ipv4_cksum,
- * payload copy, fragmentation at the MTU) and one D2H returns them.
+ * payload copy, fragmentation at the MTU, the UDP checksum with [gpu] tx_udp_cksum = 1) and one
+ * D2H returns them.
  */
 #include <errno.h>
 #include <stdlib.h>
@@ -50,6 +51,7 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
     if (!g_udpdk.gpu) { errno = ENODEV; return -1; }
     udpdk_gpu_ctx *g = g_udpdk.gpu;
     const uint32_t mtu = g_udpdk.mtu;
+    const uint32_t txf = g_udpdk.tx_udp_cksum ? UDPDK_TX_UDP_CKSUM : 0u;
     /* the slot table the TX kernel reads (source port and address per socket). tx_lock is taken
      * before the table lock is dropped (the order udpdk_close uses): a sendto that auto-binds, or
      * a close + socket + bind, either lands before the refresh (and is in the uploaded table) or
@@ -157,7 +159,7 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
                           (const int32_t *)(d + o_sock), (const uint32_t *)(d + o_ip),
                           (const uint16_t *)(d + o_port), nsel};
     udpdk_tx_out_t o = {g_udpdk.tx_fr_d, bytes + 64, (const uint32_t *)(d + o_foff)};
-    if ((rc = udpdk_gpu_h2d(g, d, h, tot)) || (rc = udpdk_gpu_tx_build_mtu(g, &cfg, &b, &o, mtu)) ||
+    if ((rc = udpdk_gpu_h2d(g, d, h, tot)) || (rc = udpdk_gpu_tx_build_flags(g, &cfg, &b, &o, mtu, txf)) ||
         (rc = udpdk_gpu_d2h(g, out, g_udpdk.tx_fr_d, bytes)) || (rc = udpdk_gpu_sync(g))) {
         errno = -rc;
         goto out;

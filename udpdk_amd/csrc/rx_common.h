@@ -427,6 +427,7 @@ void reasm_destroy(Reasm *r);
 int  reasm_run(Reasm *r, hipStream_t st, const udpdk_rx_batch_t *bt, const uint32_t *meta_dev,
                 uint64_t tms, udpdk_reasm_out_t *o, int *hip_err, bool inplace);
 
-__global__ void tx_build(TxArgs a);
+// CK: with the UDP checksum (UDPDK_TX_UDP_CKSUM; one wave per group, TxArgs::parts unused)
+template <bool CK> __global__ void tx_build(TxArgs a);
 
 } // namespace udpdk

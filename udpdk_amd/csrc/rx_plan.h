@@ -32,6 +32,7 @@ struct RxKnobs {
     uint32_t scatter_group_frames = UDPDK_SCATTER_GROUP_FRAMES;   // UDPDK_SCATTER_GROUP_FRAMES (tests, A/B)
     uint32_t scatter_min_wg = UDPDK_SCATTER_MIN_WG;               // UDPDK_SCATTER_MIN_WG (tests, A/B)
     uint32_t tx_parts = 0;         // UDPDK_TX_PARTS=1..4 (tests): TxArgs::parts, 0 = computed per batch
+                                   // (not for UDPDK_TX_UDP_CKSUM, which always runs one part)
     uint32_t tx_grid = 4096;       // UDPDK_TX_GRID>=1 (tests): tx_build's workgroup cap
     uint32_t gather_grid = 16384;  // UDPDK_GATHER_GRID>=1 (tests): rx_gather's workgroup cap
 };

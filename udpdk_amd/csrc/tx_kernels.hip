@@ -3,7 +3,8 @@
 //
 // Per datagram: Ethernet (config MACs, type 0x0800), IPv4 (0x45, tos 0, total length, id 0,
 // frag 0, ttl 64, proto 17, rte_ipv4_cksum, src = bound slot IP unless ANY else config IP,
-// dst), UDP (raw src/dst ports, length, checksum 0), then the payload.
+// dst), UDP (raw src/dst ports, length, checksum 0 or, in tx_build<true>, the RFC 768 checksum
+// over the pseudo-header, the UDP header and the payload), then the payload.
 //
 // Fragmentation (mtu != 0 and len + 42 > mtu, the poller's pkt_len > IPV4_MTU_DEFAULT test):
 // the IPv4 packet is cut the way DPDK 20.05 rte_ipv4_fragment_packet does (restated in
@@ -77,6 +78,21 @@ __device__ __forceinline__ uint32_t ipv4_cksum(uint32_t raw) { return raw == 0xF
 // The checksum a NIC computes for PKT_TX_IP_CKSUM (fragments, rte_ipv4_fragment_packet leaves 0).
 __device__ __forceinline__ uint32_t ipv4_cksum_nic(uint32_t raw) { return ~raw & 0xFFFFu; }
 
+// The RFC 768 terms that are not payload, as LE 16-bit words like ipv4_raw: the pseudo-header
+// (src, dst, zero, 17, UDP length) and the UDP header (raw ports, length, checksum field 0).
+__device__ __forceinline__ uint32_t udp_head_sum(uint32_t src, uint32_t dst, uint32_t pt, uint32_t ul)
+{
+    return sad16(src, sad16(dst, sad16(pt, 0x1100u + 2u * bswap16(ul))));
+}
+
+// The checksum field for a one's-complement sum s of everything it covers: folded,
+// complemented, and 0 sent as 0xffff (RFC 768: a transmitted 0 means "no checksum").
+__device__ __forceinline__ uint32_t udp_cksum(uint32_t s)
+{
+    const uint32_t c = ~fold32(s) & 0xFFFFu;
+    return c ? c : 0xFFFFu;
+}
+
 constexpr int TX_WIN = 64;  // bytes of header window per frame (16 dwords)
 constexpr int TXW = TX_BLOCK / 64;
 
@@ -88,6 +104,7 @@ constexpr uint32_t TX_SMALL_LOADS = (TX_SMALL_SPAN - 42u + 15u) / 16u;
 // the slot lookup (byte-aligned 16-byte buffer loads; pieces past the payload are addressed out
 // of range, so they cost no memory access and read as 0), so a wave's frames take one round
 // trip after the descriptors instead of one per 64-chunk sweep step.
+template <bool CK>
 __device__ __forceinline__ void tx_small(const TxArgs &a, uint32_t i, uint32_t fo, uint32_t L,
                                          uint32_t po, int32_t sock)
 {
@@ -123,10 +140,20 @@ __device__ __forceinline__ void tx_small(const TxArgs &a, uint32_t i, uint32_t f
     H[7] = (sq >> 16) | ((dq & 0xFFFFu) << 16);
     H[8] = (dq >> 16) | ((ptq & 0xFFFFu) << 16);
     H[9] = (ptq >> 16) | (bswap16(ul) << 16);
+    // RFC 768 checksum from the words already here: pseudo-header and UDP header, then the
+    // payload dwords masked to [0, L) (the pieces hold whatever follows the payload; the UDP
+    // header is at an even datagram offset, so payload dwords are whole 16-bit words of the sum)
+    uint32_t ck = 0u;
+    if constexpr (CK) {
+        uint32_t s = udp_head_sum(sq, dq, ptq, ul);
+#pragma unroll
+        for (uint32_t d = 0; d < (TX_SMALL_SPAN - 42u + 3u) / 4u; ++d) s = sad16(P[d] & dword_window(0, (int)L, (int)d), s);
+        ck = udp_cksum(s);
+    }
     // frame dword d: the header for d < 10; then frame byte 42 + t = payload byte t, so dword
-    // d >= 10 = payload bytes [4d - 42, 4d - 38) (bytes 40-41: UDP checksum 0)
+    // d >= 10 = payload bytes [4d - 42, 4d - 38) (bytes 40-41: UDP checksum, 0 unless CK)
     auto F = [&](uint32_t d) -> uint32_t {
-        return d < 10u ? H[d] : (d == 10u ? P[0] << 16 : __builtin_amdgcn_alignbyte(P[d - 10u], P[d - 11u], 2));
+        return d < 10u ? H[d] : (d == 10u ? (P[0] << 16) | ck : __builtin_amdgcn_alignbyte(P[d - 10u], P[d - 11u], 2));
     };
     // whole 16-byte pieces, then the frame's last 0-15 bytes as dword / byte stores
 #pragma unroll
@@ -152,6 +179,21 @@ __device__ __forceinline__ void tx_small(const TxArgs &a, uint32_t i, uint32_t f
 
 } // namespace
 
+// CK: the RFC 768 UDP checksum of every written datagram at bytes 40-41 of its first frame
+// (UDPDK_TX_UDP_CKSUM); tx_build<false> leaves them 0 as udpdk_sendto does (:343).
+//
+// tx_small sums the words in its registers. On the sweep path every chunk adds the one's-
+// complement sum of its payload bytes (the window pm) to its datagram's accumulator, and after
+// the group's last round the datagram's own lane adds the pseudo-header and UDP header terms and
+// patches the two bytes. The accumulator of the datagram in lane q is win[w][q][15]: a header
+// window is at most 15 + 42 = 57 bytes, so no header byte ever lies in a row's last dword, and
+// the CK build never writes that dword while building headers; LDS stays 20 KiB. l_len bits
+// 24-29 carry the frame's datagram lane. Byte lanes: chunks are 16-byte aligned in the output,
+// the UDP header starts at frame byte 34, fragment payload offsets and mtu + 14 are even, so
+// byte t of a datagram sits in an odd byte of its chunk's 16-bit words exactly when frame_off[i]
+// is odd, in every frame of the datagram: the chunk's folded sum is byte-swapped then (RFC 1071
+// §2(B)). One wave per group (parts is 1): the patch must follow the sweep's own zeros.
+template <bool CK>
 __global__ void __launch_bounds__(TX_BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8)))
 tx_build(TxArgs a)
 {
@@ -159,17 +201,20 @@ tx_build(TxArgs a)
     // per output frame of the current round
     // (l_len bit 31: 34-byte header, a fragment after the first)
     __shared__ uint32_t l_cs[TXW][64], l_fo[TXW][64], l_len[TXW][64], l_po[TXW][64];
-    const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
+    // (CK: the wave index as a scalar, or the work-item id is kept in a VGPR for it and spilled)
+    const uint32_t lane = lane_id();
+    const uint32_t w = CK ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : threadIdx.x >> 6;
     const __amdgpu_buffer_rsrc_t pr = make_rsrc(a.payload, a.payload_rsrc);
     const uint32_t waves_total = gridDim.x * TXW;
     const uint32_t fpl = a.mtu ? a.mtu - 20u : 0u;      // IP payload bytes per full fragment
+    const uint32_t parts = CK ? 1u : a.parts;
 
     // a.parts waves share each group of 64 datagrams: every one builds the group's headers and
     // takes every a.parts-th 64 chunks of its sweep (few large datagrams, e.g. 256 K datagrams
     // of 2952 B, are 4096 groups: one wave per group left 4 waves per SIMD, each a long sweep)
     const uint32_t groups = (a.n + 63u) / 64u;
-    for (uint32_t gp = blockIdx.x * TXW + w; gp < groups * a.parts; gp += waves_total) {
-        const uint32_t g = gp / a.parts, part = gp % a.parts;
+    for (uint32_t gp = blockIdx.x * TXW + w; gp < groups * parts; gp += waves_total) {
+        const uint32_t g = gp / parts, part = gp % parts;
         const uint32_t i = g * 64 + lane;
         uint32_t nf = 0, fo = 0, L = 0, po = 0, src = 0, dst = 0, pt = 0;
         int32_t sock = -1;
@@ -181,9 +226,11 @@ tx_build(TxArgs a)
         }
         // a wave of small unfragmented frames: one lane builds and stores its own frame
         if (!__ballot(i < a.n && (L + 42u > TX_SMALL_SPAN || (a.mtu && L + 42u > a.mtu)))) {
-            if (part == 0u) tx_small(a, i, fo, L, po, sock);
+            if (part == 0u) tx_small<CK>(a, i, fo, L, po, sock);
             continue;
         }
+        // this group's accumulators; the first round's wave_sync_tx orders them before any add
+        if constexpr (CK) win[w][lane][15] = 0u;
         if (i < a.n) {
             const bool frag = a.mtu && L + 42u > a.mtu;                    // poller.c:466
             const uint32_t n_fr = frag ? (L + 8u + fpl - 1u) / fpl : 1u;
@@ -213,6 +260,7 @@ tx_build(TxArgs a)
             uint32_t nch = 0, ffo = 0, plen = 0, ppo = 0, hl = 0;
             uint32_t k = 0, lnq = ln, sq = src, dq = dst, ptq = pt, foq = fo, poq = po;
             bool act = nf != 0;
+            uint32_t dl = lane;                   // the frame's datagram lane (CK)
             if (!direct) {
                 // the datagram of frame f: the last q with fs[q] <= f (datagrams without frames
                 // share their successor's first index); shuffles run with every lane active
@@ -231,6 +279,7 @@ tx_build(TxArgs a)
                 foq = __shfl(fo, (int)q, 64);
                 poq = __shfl(po, (int)q, 64);
                 act = f < n_frames;
+                dl = q;
             }
             const uint32_t Lq = lnq & 0xFFFFu, nfq = lnq >> 16;
             if (act) {
@@ -271,33 +320,34 @@ tx_build(TxArgs a)
                 // window byte (ffo & 15) + r
                 const uint32_t sh = ffo & 15u, s3 = sh & 3u, d0 = sh >> 2;
                 uint32_t *wq = win[w][lane];
+                // (CK: dword 15 is a datagram's accumulator, and holds no header byte)
 #pragma unroll
-                for (int t = 0; t < 16; ++t) wq[t] = 0u;
+                for (int t = 0; t < (CK ? 15 : 16); ++t) wq[t] = 0u;
 #pragma unroll
                 for (int t = 0; t < 12; ++t) {
                     const uint32_t prev = t ? h[t - 1] : 0u;
                     const uint32_t gk = s3 ? ((h[t] << (8u * s3)) | (prev >> (32u - 8u * s3))) : h[t];
                     wq[d0 + t] = gk;
                 }
-                if (s3) wq[d0 + 12] = h[11] >> (32u - 8u * s3);
+                if (s3 && (!CK || d0 < 3u)) wq[d0 + 12] = h[11] >> (32u - 8u * s3);
                 nch = ((ffo & 15u) + hl + plen + 15u) >> 4;
             }
             uint32_t total;
             const uint32_t cs = excl_scan64(nch, &total);
             l_cs[w][lane] = cs;
             l_fo[w][lane] = ffo;
-            l_len[w][lane] = plen | (hl == 34u ? 0x80000000u : 0u);
+            l_len[w][lane] = plen | (hl == 34u ? 0x80000000u : 0u) | (CK ? dl << 24 : 0u);
             l_po[w][lane] = ppo;
             wave_sync_tx();
 
-            for (uint32_t k = lane + 64u * part; k < total; k += 64u * a.parts) {
+            for (uint32_t k = lane + 64u * part; k < total; k += 64u * parts) {
                 uint32_t q = 0;
 #pragma unroll
                 for (int sft = 32; sft >= 1; sft >>= 1)
                     if (l_cs[w][q + sft] <= k) q += sft;
                 const uint32_t j = k - l_cs[w][q];
                 const uint32_t fq = l_fo[w][q], lw = l_len[w][q], pq = l_po[w][q];
-                const uint32_t Lq = lw & 0x7FFFFFFFu;
+                const uint32_t Lq = lw & (CK ? 0x00FFFFFFu : 0x7FFFFFFFu);
                 const int hq = (lw >> 31) ? 34 : 42;
                 const uint32_t abase = (fq & ~15u) + 16u * j;
                 const int r0c = (int)(abase - fq);
@@ -323,7 +373,7 @@ tx_build(TxArgs a)
                         P[t] = __builtin_amdgcn_alignbyte(hi, lo, s);
                     }
                 }
-                uint32_t o[4], own[4];
+                uint32_t o[4], own[4], psum = 0u;
                 bool full = true;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
@@ -332,6 +382,18 @@ tx_build(TxArgs a)
                     o[t] = (H[t] & hm) | (P[t] & pm);
                     own[t] = hm | pm;
                     full = full && own[t] == 0xFFFFFFFFu;
+                    if constexpr (CK) psum = sad16(P[t] & pm, psum);
+                }
+                if constexpr (CK) {
+                    // The chunk's payload bytes, folded, in the datagram's byte lanes. Lanes of
+                    // one frame add to one LDS word and the adds serialise; a run-wise reduction
+                    // first (DPP prefix sums, one add per run of lanes) was measured slower on
+                    // every shape, so the plain add stays.
+                    if (psum) {
+                        psum = fold32(psum);
+                        if (fq & 1u) psum = bswap16(psum);
+                        atomicAdd(&win[w][(lw >> 24) & 63u][15], psum);
+                    }
                 }
                 uint8_t *dstp = a.frames + abase;
                 if (full) {
@@ -350,7 +412,21 @@ tx_build(TxArgs a)
             }
             wave_sync_tx();
         }
+        if constexpr (CK) {
+            // The datagram's own lane finishes its sum and patches bytes 40-41 of its first
+            // frame (fo may be odd: two byte stores). The sweep wrote zeros there; the closing
+            // wave_sync_tx of the last round drained this wave's stores and LDS adds before this
+            // point, and no other wave writes this group's frames. Skipped datagrams: no patch.
+            if (nf) {
+                const uint32_t ck = udp_cksum(win[w][lane][15] + udp_head_sum(src, dst, pt, L + 8u));
+                a.frames[fo + 40u] = (uint8_t)ck;
+                a.frames[fo + 41u] = (uint8_t)(ck >> 8);
+            }
+        }
     }
 }
+
+template __global__ void tx_build<false>(TxArgs a);
+template __global__ void tx_build<true>(TxArgs a);
 
 } // namespace udpdk

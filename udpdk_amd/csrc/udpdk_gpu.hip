@@ -1302,7 +1302,15 @@ int udpdk_gpu_tx_build(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udp
 int udpdk_gpu_tx_build_mtu(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
                            const udpdk_tx_batch_t *bt, const udpdk_tx_out_t *o, uint32_t mtu)
 {
+    return udpdk_gpu_tx_build_flags(c, cfg, bt, o, mtu, 0u);
+}
+
+int udpdk_gpu_tx_build_flags(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
+                             const udpdk_tx_batch_t *bt, const udpdk_tx_out_t *o, uint32_t mtu,
+                             uint32_t flags)
+{
     if (!c || !cfg || !bt || !o) return -EINVAL;
+    if (flags & ~UDPDK_TX_UDP_CKSUM) return -EINVAL;
     if (mtu && (mtu < 68u || mtu > 65535u || (mtu - 20u) % 8u)) return -EINVAL;
     if (!bt->n) return 0;
     if (!bt->payload_dev || !bt->payload_off_dev || !bt->payload_len_dev || !bt->sockfd_dev ||
@@ -1341,8 +1349,13 @@ int udpdk_gpu_tx_build_mtu(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
     // ~16 K waves (their chunk sweeps split between them)
     ta.parts = std::max<uint32_t>(1u, std::min<uint32_t>(4u, 16384u / std::max<uint32_t>(groups, 1u)));
     if (c->knobs.tx_parts) ta.parts = c->knobs.tx_parts;
+    // the checksum form: one wave per group (a datagram's sum is kept by the wave that sweeps
+    // it and patched in behind that wave's own stores); UDPDK_TX_PARTS does not apply
+    if (flags & UDPDK_TX_UDP_CKSUM) ta.parts = 1u;
     const uint32_t grid = std::min<uint32_t>(ceil_div(groups * ta.parts, TX_BLOCK / 64), c->knobs.tx_grid);
-    return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build, dim3(grid), dim3(TX_BLOCK), ta);
+    if (flags & UDPDK_TX_UDP_CKSUM)
+        return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<true>, dim3(grid), dim3(TX_BLOCK), ta);
+    return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<false>, dim3(grid), dim3(TX_BLOCK), ta);
 }
 
 #ifdef UDPDK_STAMPS
