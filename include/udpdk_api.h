@@ -178,6 +178,18 @@ int udpdk_config_mtu(uint32_t mtu);
  * included. One switch for the whole library, taking effect from the next drain. Returns the
  * setting in force before the call (0 or 1); a negative `on` only reads it; on > 1: -1, EINVAL. */
 int udpdk_config_tx_cksum(int on);
+/* Received deliveries that fail their checksums or lengths (ini: [gpu] rx_drop = none | all | a
+ * comma list of ip, udp, len, ihl). flags: UDPDK_RX_DROP_* bits (udpdk_gpu.h). 0 (default): every
+ * delivery reaches its socket, as the reference hands them on; otherwise udpdk_poll_rx takes the
+ * deliveries with a selected failure out of the lanes on the GPU (udpdk_gpu_rx_drop) before ring
+ * admission, datagrams reassembled from fragments included, and recvfrom never sees them (RFC 1122
+ * §4.1.3.4). One setting for the whole library, applied to every context by the next poll. Returns
+ * the flags in force before the call; a negative argument only reads them; a bit outside
+ * UDPDK_RX_DROP_ALL: -1, EINVAL. */
+int udpdk_config_rx_drop(int flags);
+/* Deliveries removed that way, summed over polls (and their shards and chunks) of the library
+ * session, like udpdk_rx_nobufs. */
+uint64_t udpdk_rx_dropped(void);
 
 /* Socket slot state (exch_slot_info, udpdk_types.h:40-47) for the GPU TX slot table. */
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots);

@@ -44,8 +44,8 @@ extern "C" {
 /* 2: udpdk_reasm_out_t stats grew to UDPDK_RS_N = 11 (RS_SERIAL, RS_SORTED);
  *    udpdk_gpu_rx_gather_packed; TX payloads need UDPDK_GPU_FRAMES_TAILROOM readable bytes
  * 3: udpdk_frag_table_cfg_t grew max_entries (the table's LRU limit) and flags (32 bytes)
- *    (still 3: udpdk_gpu_tx_build_flags / UDPDK_TX_UDP_CKSUM were added; a new symbol breaks no
- *    caller) */
+ *    (still 3: udpdk_gpu_tx_build_flags / UDPDK_TX_UDP_CKSUM, then udpdk_gpu_rx_filter /
+ *    udpdk_gpu_rx_drop / udpdk_gpu_rx_drop_stats were added; a new symbol breaks no caller) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -287,6 +287,69 @@ int udpdk_gpu_pipe_wait(udpdk_gpu_ctx *ctx, int pipe);
 int udpdk_gpu_pipe_batch(udpdk_gpu_ctx *ctx, int pipe, udpdk_rx_batch_t *batch, const uint32_t **meta_dev);
 int udpdk_gpu_pipe_h2d(udpdk_gpu_ctx *ctx, int pipe, void *dev, const void *host, size_t bytes);
 int udpdk_gpu_pipe_d2h(udpdk_gpu_ctx *ctx, int pipe, void *host, const void *dev, size_t bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * RX drop filter: deliveries whose checksums or lengths fail are taken out of the lanes (RFC 1122
+ * §4.1.3.4 has a UDP stack discard a datagram with a failed checksum; the reference delivers it).
+ * rx_classify only flags such frames in their verdict word; this optional stage after the lanes
+ * are complete removes every lane entry e = lane_pkt[p] whose meta[e] shows a selected reason.
+ * Arrival order inside each lane is kept; the new lane_off[l] is the number of kept entries before
+ * position lane_off[l]. Off by default: with no flags set udpdk_gpu_rx enqueues what it always did.
+ *
+ * An entry is removed when any selected reason applies. (A bad UDP length also makes the UDP
+ * checksum state BAD: UDPDK_RX_DROP_UDP_LEN alone selects a subset of UDPDK_RX_DROP_UDP_CKSUM.)
+ * ------------------------------------------------------------------------------------------- */
+#define UDPDK_RX_DROP_IP_CKSUM  1u   /* UDPDK_META_IP_OK(m) == 0                            */
+#define UDPDK_RX_DROP_UDP_CKSUM 2u   /* UDPDK_META_UDP_CSUM(m) == UDPDK_UDP_CSUM_BAD        */
+#define UDPDK_RX_DROP_UDP_LEN   4u   /* UDPDK_META_LEN_BAD(m)                               */
+#define UDPDK_RX_DROP_IHL       8u   /* UDPDK_META_IHL_NE5(m)                               */
+#define UDPDK_RX_DROP_ALL       15u
+
+typedef struct {
+    const uint32_t *meta_dev;      /* [n] */
+    uint32_t        n;
+    const uint32_t *lane_off_dev;  /* [n_lanes + 1] */
+    const uint32_t *lane_pkt_dev;  /* entries [0, min(lane_off[n_lanes], lane_cap)) are read */
+    uint32_t        lane_cap;
+    uint32_t        n_lanes;       /* 1..UDPDK_GPU_MAX_LANES, need not be the snapshot's */
+} udpdk_rx_lanes_t;
+
+/* The filter as an explicit call on any lane set: out of place, async on the context stream; the
+ * outputs (lane_off_out_dev[n_lanes + 1], lane_pkt_out_dev[out_cap]) must not alias the inputs.
+ * flags == 0 is a valid identity copy (only entries >= n are removed); bits outside
+ * UDPDK_RX_DROP_ALL give -EINVAL. meta is only read. Bounds, whatever the inputs hold: an offset
+ * beyond min(lane_off[n_lanes], lane_cap) counts as that, an entry >= n is removed without a meta
+ * read (bad_index), nothing past lane_cap is read and nothing past out_cap written; when more
+ * than out_cap entries are kept only the first out_cap are written, lane_off_out is complete and
+ * udpdk_gpu_rx_drop_stats returns -ENOSPC. */
+int udpdk_gpu_rx_filter(udpdk_gpu_ctx *ctx, const udpdk_rx_lanes_t *in, uint32_t flags,
+                        uint32_t *lane_off_out_dev, uint32_t *lane_pkt_out_dev, uint32_t out_cap);
+
+/* Sticky mode: with nonzero flags every later udpdk_gpu_rx / udpdk_gpu_rx_host /
+ * udpdk_gpu_rx_host_async / udpdk_gpu_pipe_rx_host call on this context filters its lanes, on the
+ * call's own stream, before anything reads them (the caller's lane_off and lane_pkt hold the
+ * filtered set; pipeline depths 2-4 work as before); with flags 0 (default) no filter stage is
+ * enqueued at all. Returns the previous flags; a negative argument only queries; bits outside
+ * UDPDK_RX_DROP_ALL give -EINVAL.
+ *   - meta is never rewritten: it still says what classify found, fan-out and sockfd included.
+ *   - udpdk_rx_stats_t: counters[] (UDPDK_C_DELIVERIES too) stay classify's; deliveries becomes
+ *     the kept count, so it still equals lane_off[n_lanes]; overflow and -ENOSPC are still decided
+ *     by the pre-filter total against lane_cap, and after an overflow the filtered lanes are those
+ *     of the truncated input.
+ *   - udpdk_gpu_rx_gather* and reassembly are unchanged: they consume the lanes they are given. */
+int udpdk_gpu_rx_drop(udpdk_gpu_ctx *ctx, int flags);
+
+typedef struct {
+    uint64_t dropped[4];   /* entries per reason (ip, udp, len, ihl); an entry counts under every
+                              selected reason that applies */
+    uint32_t kept, removed;
+    uint32_t bad_index;    /* entries >= n: removed, meta never read */
+    uint32_t truncated;    /* input lane_off[n_lanes] > lane_cap: only the first lane_cap seen */
+} udpdk_rx_drop_stats_t;
+/* Of the last filter run on the context (explicit or sticky; -ENOENT when there was none).
+ * Synchronises. -ENOSPC if kept > out_cap (sticky mode: the call's lane_cap, which cannot
+ * happen). The filter launches are not event-timed (udpdk_gpu_timing_read). */
+int udpdk_gpu_rx_drop_stats(udpdk_gpu_ctx *ctx, udpdk_rx_drop_stats_t *stats);
 
 /* ---------------------------------------------------------------------------------------------
  * RX payload delivery: the batch form of udpdk_recvfrom (udpdk_syscall.c:401-488) over the lane

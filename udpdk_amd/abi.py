@@ -77,6 +77,20 @@ class RxStats(C.Structure):
                 ("overflow", C.c_uint32)]
 
 
+# UDPDK_RX_DROP_*: the deliveries the RX drop filter removes
+RX_DROP_IP_CKSUM, RX_DROP_UDP_CKSUM, RX_DROP_UDP_LEN, RX_DROP_IHL, RX_DROP_ALL = 1, 2, 4, 8, 15
+
+
+class RxLanes(C.Structure):
+    _fields_ = [("meta_dev", C.c_void_p), ("n", C.c_uint32), ("lane_off_dev", C.c_void_p),
+                ("lane_pkt_dev", C.c_void_p), ("lane_cap", C.c_uint32), ("n_lanes", C.c_uint32)]
+
+
+class RxDropStats(C.Structure):
+    _fields_ = [("dropped", C.c_uint64 * 4), ("kept", C.c_uint32), ("removed", C.c_uint32),
+                ("bad_index", C.c_uint32), ("truncated", C.c_uint32)]
+
+
 class RxGather(C.Structure):
     _fields_ = [("payload_dev", C.c_void_p), ("slot_bytes", C.c_uint32), ("len_dev", C.c_void_p),
                 ("src_ip_dev", C.c_void_p), ("src_port_dev", C.c_void_p)]
@@ -175,6 +189,9 @@ _PROTOS = {
     "udpdk_gpu_pipe_d2h": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t]),
     "udpdk_gpu_pipe_gather_packed": (C.c_int, [_P, C.c_int, C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32,
                                                _P, C.POINTER(RxGather)]),
+    "udpdk_gpu_rx_filter": (C.c_int, [_P, C.POINTER(RxLanes), C.c_uint32, _P, _P, C.c_uint32]),
+    "udpdk_gpu_rx_drop": (C.c_int, [_P, C.c_int]),
+    "udpdk_gpu_rx_drop_stats": (C.c_int, [_P, C.POINTER(RxDropStats)]),
     "udpdk_gpu_rx_gather": (C.c_int, [_P, C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32,
                                       C.POINTER(RxGather)]),
     "udpdk_gpu_rx_gather_packed": (C.c_int, [_P, C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32, _P,
@@ -218,6 +235,8 @@ _PROTOS = {
     "udpdk_config_get": (C.c_int, [_P, _P, C.POINTER(C.c_uint32)]),
     "udpdk_config_mtu": (C.c_int, [C.c_uint32]),
     "udpdk_config_tx_cksum": (C.c_int, [C.c_int]),
+    "udpdk_config_rx_drop": (C.c_int, [C.c_int]),
+    "udpdk_rx_dropped": (C.c_uint64, []),
     "udpdk_tx_pending": (C.c_uint64, []),
     "udpdk_tx_dropped": (C.c_uint64, []),
     "udpdk_rx_nobufs": (C.c_uint64, []),
@@ -391,6 +410,14 @@ class GpuContext:
         _check(lib().udpdk_gpu_bind_snapshot_upload(self.handle, C.byref(hs.snap)),
                "udpdk_gpu_bind_snapshot_upload")
 
+    def rx_drop(self, flags: int) -> int:
+        """Sticky RX drop filter (udpdk_gpu_rx_drop): RX_DROP_* flags for every later RX call on
+        the context; returns the previous flags, a negative argument only reads them."""
+        rc = lib().udpdk_gpu_rx_drop(self.handle, int(flags))
+        if rc < 0:
+            _check(rc, "udpdk_gpu_rx_drop")
+        return rc
+
     def timing(self, every: int):
         """0 = off, N = record kernel events on every Nth udpdk_gpu_rx call."""
         _check(lib().udpdk_gpu_timing_enable(self.handle, int(every)), "timing_enable")
@@ -468,6 +495,42 @@ def rx_run(ctx: GpuContext, b: RxDeviceBatch, o: RxDeviceOut):
     d = min(int(st.deliveries), o.lane_cap)
     pkt = ctx.download(o.lane_pkt, np.uint32, d)
     return meta, loff, pkt, np.array(st.counters[:], np.uint64), rc
+
+
+def rx_drop_stats(ctx: GpuContext) -> tuple[int, RxDropStats]:
+    st = RxDropStats()
+    rc = lib().udpdk_gpu_rx_drop_stats(ctx.handle, C.byref(st))
+    return rc, st
+
+
+def rx_filter_run(ctx: GpuContext, meta: np.ndarray, lane_off: np.ndarray, lane_pkt: np.ndarray,
+                  flags: int, *, n: int | None = None, lane_cap: int | None = None,
+                  out_cap: int | None = None, pad: int = 0, fill: int = 0xA5A5A5A5):
+    """udpdk_gpu_rx_filter over host arrays: upload, run, download. lane_pkt is uploaded whole
+    (lane_cap defaults to its length, so a caller may pass more than lane_off[-1] entries); the
+    entry output buffer has out_cap + pad words, all pre-filled with `fill`. Returns (lane_off_out,
+    lane_pkt_out[out_cap + pad], RxDropStats, rc of udpdk_gpu_rx_drop_stats)."""
+    meta = np.ascontiguousarray(meta, np.uint32)
+    lane_off = np.ascontiguousarray(lane_off, np.uint32)
+    lane_pkt = np.ascontiguousarray(lane_pkt, np.uint32)
+    n = len(meta) if n is None else n
+    lane_cap = len(lane_pkt) if lane_cap is None else lane_cap
+    out_cap = lane_cap if out_cap is None else out_cap
+    n_lanes = len(lane_off) - 1
+    bufs = [ctx.upload(meta), ctx.upload(lane_off), ctx.upload(lane_pkt),
+            ctx.upload(np.full(n_lanes + 1, fill, np.uint32)),
+            ctx.upload(np.full(out_cap + pad, fill, np.uint32))]
+    md, od, pd, oo, po = bufs
+    try:
+        lanes = RxLanes(md.ptr, n, od.ptr, pd.ptr, lane_cap, n_lanes)
+        _check(lib().udpdk_gpu_rx_filter(ctx.handle, C.byref(lanes), flags, C.c_void_p(oo.ptr),
+                                         C.c_void_p(po.ptr), out_cap), "udpdk_gpu_rx_filter")
+        rc, st = rx_drop_stats(ctx)
+        return (ctx.download(oo, np.uint32, n_lanes + 1), ctx.download(po, np.uint32, out_cap + pad),
+                st, rc)
+    finally:
+        for b in bufs:
+            b.free()
 
 
 @dataclass
@@ -710,6 +773,14 @@ class HostApi:
         """UDP checksum on sent datagrams (udpdk_config_tx_cksum): returns the previous setting;
         a negative `on` only reads it."""
         return self.L.udpdk_config_tx_cksum(int(on))
+
+    def config_rx_drop(self, flags: int) -> int:
+        """Deliveries udpdk_poll_rx drops for failed checksums or lengths (udpdk_config_rx_drop,
+        RX_DROP_* flags): returns the previous flags; a negative argument only reads them."""
+        return self.L.udpdk_config_rx_drop(int(flags))
+
+    def rx_dropped(self) -> int:
+        return int(self.L.udpdk_rx_dropped())
 
     def snapshot(self, compat: bool = False) -> BindSnapshot:
         snap = BindSnapshot()

@@ -140,6 +140,10 @@ struct h_state {
     uint32_t mtu;                /* IPV4_MTU_DEFAULT = RTE_ETHER_MTU (udpdk_constants.h:37)      */
     uint32_t tx_udp_cksum;       /* [gpu] tx_udp_cksum / udpdk_config_tx_cksum: udpdk_tx_drain builds
                                     with UDPDK_TX_UDP_CKSUM (0: checksum 0, udpdk_syscall.c:343) */
+    uint32_t rx_drop;            /* [gpu] rx_drop / udpdk_config_rx_drop: UDPDK_RX_DROP_* flags the next
+                                    poll sets on every context (udpdk_gpu_rx_drop)                 */
+    uint32_t rx_drop_applied;    /* ... and what the contexts hold (fresh contexts: 0)           */
+    uint64_t rx_dropped;         /* deliveries removed that way (udpdk_rx_dropped)                */
     udpdk_gpu_ctx *gpu;
     int      gpu_device;
     uint32_t gpu_max_frames, gpu_max_lanes;

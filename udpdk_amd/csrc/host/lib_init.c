@@ -40,6 +40,7 @@ static void h_config_defaults(void)
     g_udpdk.frag_max_entries = 0;      /* NUM_FLOWS_MAX (rx_poll.c: h_frag_max_entries) */
     g_udpdk.frag_flags = 0;            /* RFC 1071 header checksum on reassembled datagrams */
     g_udpdk.tx_udp_cksum = 0;          /* UDP checksum 0 on TX, udpdk_syscall.c:343 */
+    g_udpdk.rx_drop = 0;               /* every delivery reaches its socket, as in the reference */
     g_udpdk.arena_bytes_max = 4ull << 30;
     g_udpdk.arena_count_max = 1024;
     g_udpdk.port_spec[0] = g_udpdk.port_peer[0] = 0;
@@ -72,6 +73,7 @@ void udpdk_host_reset(void)
     g_udpdk.snap_version = UINT64_MAX;
     g_udpdk.mtu = 1500;
     g_udpdk.tx_udp_cksum = 0;
+    g_udpdk.rx_drop = 0;
     pthread_mutex_unlock(&g_udpdk.lock);
 }
 
@@ -178,6 +180,31 @@ int udpdk_shard_plan(const char *cfg_path, int *devices, int max)
     return n;
 }
 
+/* "[gpu] rx_drop": none | all | a comma list of ip, udp, len, ihl -> UDPDK_RX_DROP_* flags, or -1. */
+static int h_parse_rx_drop(const char *v)
+{
+    if (!strcmp(v, "none")) return 0;
+    if (!strcmp(v, "all")) return (int)UDPDK_RX_DROP_ALL;
+    static const struct { const char *name; uint32_t flag; } names[] = {
+        {"ip", UDPDK_RX_DROP_IP_CKSUM}, {"udp", UDPDK_RX_DROP_UDP_CKSUM},
+        {"len", UDPDK_RX_DROP_UDP_LEN}, {"ihl", UDPDK_RX_DROP_IHL}};
+    uint32_t fl = 0;
+    const char *p = v;
+    for (;;) {
+        while (*p == ' ' || *p == '\t') p++;
+        size_t l = strcspn(p, ", \t");
+        uint32_t f = 0;
+        for (size_t i = 0; i < sizeof(names) / sizeof(names[0]); i++)
+            if (strlen(names[i].name) == l && !strncmp(p, names[i].name, l)) f = names[i].flag;
+        if (!f) return -1;
+        fl |= f;
+        p += l;
+        while (*p == ' ' || *p == '\t') p++;
+        if (!*p) return (int)fl;
+        if (*p++ != ',') return -1;
+    }
+}
+
 /* Minimal INI reader for the keys the reference understands plus a [gpu] section. */
 static int h_load_ini(const char *path)
 {
@@ -246,6 +273,11 @@ static int h_load_ini(const char *path)
              * checksum 0 as the reference sends (udpdk_syscall.c:343) */
             if (!strcmp(v, "0") || !strcmp(v, "1")) udpdk_config_tx_cksum(v[0] - '0');
             else { rc = -1; break; }
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "rx_drop")) {
+            /* none (default) | all | a comma list of ip, udp, len, ihl: the deliveries a poll
+             * takes out of the lanes before ring admission (UDPDK_RX_DROP_*) */
+            const int fl = h_parse_rx_drop(v);
+            if (fl < 0 || udpdk_config_rx_drop(fl) < 0) { rc = -1; break; }
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port")) {
             snprintf(g_udpdk.port_spec, sizeof(g_udpdk.port_spec), "%s", v);
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port_peer")) {
@@ -276,6 +308,7 @@ int udpdk_init(int argc, char *argv[])
     int rc = udpdk_gpu_ctx_create(g_udpdk.gpu_device, g_udpdk.gpu_max_frames,
                                   g_udpdk.gpu_max_lanes, &g_udpdk.gpu);
     if (rc) { errno = rc == -ENODEV ? ENODEV : -rc; g_udpdk.gpu = NULL; return -1; }
+    g_udpdk.rx_drop_applied = 0;       /* new contexts drop nothing until a poll sets them */
     /* [gpu] devices with two or more entries: one RX shard context per entry (SURVEY.md §7 step
      * 8); a poll splits its batch into that many contiguous shards */
     if (g_udpdk.n_shards > 1) {
@@ -380,6 +413,14 @@ int udpdk_config_tx_cksum(int on)
     const int was = (int)g_udpdk.tx_udp_cksum;
     if (on > 1) { errno = EINVAL; return -1; }
     if (on >= 0) g_udpdk.tx_udp_cksum = (uint32_t)on;
+    return was;
+}
+
+int udpdk_config_rx_drop(int flags)
+{
+    const int was = (int)g_udpdk.rx_drop;
+    if (flags >= 0 && ((uint32_t)flags & ~UDPDK_RX_DROP_ALL)) { errno = EINVAL; return -1; }
+    if (flags >= 0) g_udpdk.rx_drop = (uint32_t)flags;
     return was;
 }
 

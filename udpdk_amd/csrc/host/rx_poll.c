@@ -213,6 +213,31 @@ static int h_desc_disjoint(const uint32_t *offset, const uint16_t *length, uint3
     return 1;
 }
 
+/* [gpu] rx_drop / udpdk_config_rx_drop: the setting goes to the main context and every shard
+ * context before a poll issues RX (compared once per poll; every RX call of the poll, the pass
+ * over reassembled datagrams included, runs on one of these contexts). */
+static int h_rx_drop_apply(void)
+{
+    const uint32_t want = g_udpdk.rx_drop;
+    if (want == g_udpdk.rx_drop_applied) return 0;
+    int rc = udpdk_gpu_rx_drop(g_udpdk.gpu, (int)want);
+    for (uint32_t k = 0; rc >= 0 && g_udpdk.n_shards > 1 && k < g_udpdk.n_shards; k++)
+        rc = udpdk_gpu_rx_drop(g_udpdk.shard[k].g, (int)want);
+    if (rc < 0) { errno = -rc; return -1; }
+    g_udpdk.rx_drop_applied = want;
+    return 0;
+}
+
+/* What the drop filter removed from one RX result: its counters are classify's (every delivery
+ * made) and its deliveries the kept count. (The polls size lane_cap for every delivery, so no
+ * input is truncated and the difference is the filter's `removed`.) */
+static void h_rx_drop_count(const udpdk_rx_stats_t *st)
+{
+    if (g_udpdk.rx_drop_applied && st->counters[UDPDK_C_DELIVERIES] > st->deliveries)
+        __atomic_fetch_add(&g_udpdk.rx_dropped, st->counters[UDPDK_C_DELIVERIES] - st->deliveries,
+                           __ATOMIC_RELAXED);
+}
+
 static int h_frag_pass(const udpdk_rx_batch_t *staged, const uint32_t *meta_dev, uint64_t nfrag,
                        uint32_t lanes, uint32_t maxfan, int inplace, udpdk_rx_batch_t *rb, uint32_t *nd)
 {
@@ -257,7 +282,8 @@ static int h_frag_pass(const udpdk_rx_batch_t *staged, const uint32_t *meta_dev,
     udpdk_rx_out_t o2 = {g_udpdk.dv_meta2, g_udpdk.dv_loff2, g_udpdk.dv_lpkt2, cap};
     udpdk_rx_stats_t st2;
     if ((rc = udpdk_gpu_rx(g, &ro.batch, &o2)) || (rc = udpdk_gpu_rx_stats(g, &st2))) { errno = -rc; return -1; }
-    const uint32_t D = st2.deliveries;
+    h_rx_drop_count(&st2);
+    const uint32_t D = st2.deliveries;                 /* with [gpu] rx_drop: the kept ones */
     if (h_grow_host((void **)&g_udpdk.fr_lpkt, &g_udpdk.fr_lpkt_cap, 4ull * D + 4)) return -1;
     if ((rc = udpdk_gpu_d2h(g, g_udpdk.fr_loff, g_udpdk.dv_loff2, 4ull * (lanes + 1))) ||
         (rc = udpdk_gpu_d2h(g, g_udpdk.fr_lpkt, g_udpdk.dv_lpkt2, 4ull * D)) ||
@@ -1142,6 +1168,7 @@ static int h_poll_chunked(const uint8_t *frames, uint64_t frames_bytes, const ui
         for (uint32_t v = 0; v < UDPDK_N_COUNTERS; v++) tot.counters[v] += C->st.counters[v];
         tot.deliveries += C->st.deliveries;
         tot.overflow |= C->st.overflow;
+        h_rx_drop_count(&C->st);
         udpdk_rx_batch_t staged, rb;
         const uint32_t *meta_dev = NULL;
         if ((rc = udpdk_gpu_pipe_batch(g, h_pipe_of(k), &staged, &meta_dev))) { err = -rc; break; }
@@ -1240,6 +1267,7 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
     struct h_arena *ad = NULL, *af = NULL;
     PROF_T(p0);
     if (h_snapshot_refresh()) goto out;
+    if (h_rx_drop_apply()) goto out;
     PROF_T(p1);
     const uint32_t lanes = g_udpdk.snap_lanes, maxfan = g_udpdk.snap_maxfan;
     if (g_udpdk.n_shards <= 1) {
@@ -1265,6 +1293,7 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
                                     cap, &st))) { errno = -rc; goto out; }
         if ((rc = udpdk_gpu_rx_host_batch(g, &staged, &meta_dev))) { errno = -rc; goto out; }
     }
+    h_rx_drop_count(&st);
     PROF_T(p2);
     udpdk_rx_batch_t rb;
     uint32_t nd = 0;

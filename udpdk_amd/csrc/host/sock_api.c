@@ -212,6 +212,8 @@ void h_arenas_free_all(void)
 
 uint64_t udpdk_rx_nobufs(void) { return __atomic_load_n(&g_udpdk.rx_nobufs, __ATOMIC_RELAXED); }
 
+uint64_t udpdk_rx_dropped(void) { return __atomic_load_n(&g_udpdk.rx_dropped, __ATOMIC_RELAXED); }
+
 /* ---- TX rings ----------------------------------------------------------------------------- */
 void h_tx_reset(void)
 {
@@ -260,6 +262,7 @@ void h_sockets_reset(void)
     g_udpdk.tx_queued = 0;
     g_udpdk.tx_dropped = 0;
     __atomic_store_n(&g_udpdk.rx_nobufs, 0, __ATOMIC_RELAXED);   /* per library session */
+    __atomic_store_n(&g_udpdk.rx_dropped, 0, __ATOMIC_RELAXED);
     g_udpdk.version++;
 }
 

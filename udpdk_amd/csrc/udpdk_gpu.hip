@@ -19,6 +19,7 @@
 #include "udpdk_gpu.h"
 #include "rx_common.h"
 #include "rx_plan.h"
+#include "rx_filter.h"
 
 using namespace udpdk;
 
@@ -45,6 +46,20 @@ struct TimingSet {
     bool used[TIMED_KERNELS];
 };
 
+// Workspace of the lane filter stage (rx_filter.hip), lazily sized: one per pipe for the sticky mode
+// (udpdk_gpu_rx_drop) and one for explicit udpdk_gpu_rx_filter calls.
+struct FilterWs {
+    unsigned long long *mask = nullptr; size_t mask_cap = 0;
+    uint32_t *row = nullptr; size_t row_cap = 0;
+    uint32_t *base = nullptr; size_t base_cap = 0;
+    uint32_t *pkt = nullptr; size_t pkt_cap = 0;      // sticky mode: the filtered set before it
+    uint32_t *off = nullptr; size_t off_cap = 0;      // goes back into the caller's buffers
+    FilterResult *res = nullptr; size_t res_cap = 0;
+    FilterResult *h_res = nullptr; size_t h_res_cap = 0;   // pinned mirror
+    hipStream_t stream = nullptr;                     // of the last run
+    uint32_t out_cap = 0;
+};
+
 // One RX pipe = a stream and the per-call workspace. With pipelining depth d > 1, consecutive
 // udpdk_gpu_rx calls rotate over d pipes, so one batch's prologue, tail and compaction overlap
 // the other batches' streaming phases (the calls are independent: distinct batches and output
@@ -68,6 +83,8 @@ struct Pipe {
     bool dirty = false;                       // work enqueued since the last join
     uint32_t last_tiles = 0;                  // tiles of this pipe's last call (counter rows)
     uint32_t last_lane_cap = 0;
+    FilterWs flt;                             // sticky drop filter
+    bool filtered = false;                    // this pipe's last call ran it
     // host-resident batches (udpdk_gpu_rx_host[_async]): staging, lazily sized
     uint8_t *st_frames_d = nullptr; size_t st_frames_dcap = 0;
     uint8_t *st_frames_h = nullptr; size_t st_frames_hcap = 0;
@@ -122,6 +139,10 @@ struct udpdk_gpu_ctx {
     RxCaps caps{};                            // entries of each pipe's hist / partial / tile_cnt
 
     uint64_t host_calls = 0;                  // udpdk_gpu_rx_host_async calls (pipe choice)
+
+    uint32_t drop_flags = 0;                  // udpdk_gpu_rx_drop: UDPDK_RX_DROP_* (0: no stage)
+    FilterWs xflt;                            // explicit udpdk_gpu_rx_filter calls
+    FilterWs *flt_last = nullptr;             // the last filter run (udpdk_gpu_rx_drop_stats)
 
     unsigned long long *dbg = nullptr;        // diagnostic stamp buffer (UDPDK_STAMPS builds)
     Reasm *reasm = nullptr;                   // udpdk_gpu_frag_table_create
@@ -398,6 +419,13 @@ int udpdk_gpu_ctx_destroy(udpdk_gpu_ctx *c)
         if (p) (void)hipFree(p);
     void *dev[] = {c->port_tab, c->binds, c->slots};
     for (void *p : dev) if (p) (void)hipFree(p);
+    FilterWs *fw[MAX_PIPES + 1] = {&c->xflt};
+    for (int i = 0; i < MAX_PIPES; ++i) fw[i + 1] = &c->pipes[i].flt;
+    for (FilterWs *W : fw) {
+        void *pd[] = {W->mask, W->row, W->base, W->pkt, W->off, W->res};
+        for (void *p : pd) if (p) (void)hipFree(p);
+        if (W->h_res) (void)hipHostFree(W->h_res);
+    }
     for (Pipe &P : c->pipes) {
         void *ph[] = {P.st_frames_h, P.st_desc_h};
         for (void *p : ph) if (p) (void)hipHostFree(p);
@@ -609,7 +637,78 @@ int udpdk_gpu_timing_read(udpdk_gpu_ctx *c, double ms[UDPDK_N_KERNEL_IDS],
 
 namespace {
 
+// The lane filter (rx_filter.hip) over one lane set on stream st: mark, base, write.
+int filter_enqueue(udpdk_gpu_ctx *c, FilterWs &W, hipStream_t st, const udpdk_rx_lanes_t *in, uint32_t flags,
+                   uint32_t *off_out, uint32_t *pkt_out, uint32_t out_cap)
+{
+    const uint32_t tiles = ceil_div(in->lane_cap, FLT_TILE);
+    int rc;
+    if ((rc = ensure_dev(c, (void **)&W.mask, &W.mask_cap, ((size_t)tiles * FLT_CHUNKS + 1) * 8)) ||
+        (rc = ensure_dev(c, (void **)&W.row, &W.row_cap, ((size_t)tiles * FLT_ROW + 1) * 4)) ||
+        (rc = ensure_dev(c, (void **)&W.base, &W.base_cap, ((size_t)tiles + 1) * 4)) ||
+        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(FilterResult))) ||
+        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(FilterResult))))
+        return rc;
+    FilterArgs fa;
+    fa.meta = in->meta_dev;
+    fa.lane_off = in->lane_off_dev;
+    fa.lane_pkt = in->lane_pkt_dev;
+    fa.lane_off_out = off_out;
+    fa.lane_pkt_out = pkt_out;
+    fa.mask = W.mask;
+    fa.row = W.row;
+    fa.base = W.base;
+    fa.res = W.res;
+    fa.n = in->n;
+    fa.lane_cap = in->lane_cap;
+    fa.n_lanes = in->n_lanes;
+    fa.flags = flags;
+    fa.out_cap = out_cap;
+    fa.n_tiles = tiles;
+    if (tiles) {
+        hipLaunchKernelGGL(rx_filter_mark, dim3(tiles), dim3(FLT_BLOCK), 0, st, fa);
+        HIPC(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(rx_filter_base, dim3(1), dim3(FLT_BASE_BLOCK), 0, st, fa);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(rx_filter_write, dim3(tiles + ceil_div(in->n_lanes + 1u, (uint32_t)FLT_BLOCK)),
+                       dim3(FLT_BLOCK), 0, st, fa);
+    HIPC(c, hipGetLastError());
+    W.stream = st;
+    W.out_cap = out_cap;
+    c->flt_last = &W;
+    return 0;
+}
+
+int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udpdk_rx_out_t *o);
+
+// One batch's RX on a pipe: the launch sequence that makes the lanes (whichever form it takes),
+// then, in sticky drop mode, the filter from the caller's buffers into the pipe's workspace and
+// the filtered set back into the caller's buffers, all on the pipe's stream.
 int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udpdk_rx_out_t *o)
+{
+    int rc = rx_lanes_on_pipe(c, pipe, bt, o);
+    if (rc) return rc;
+    Pipe &P = c->pipes[pipe];
+    P.filtered = false;
+    if (!c->drop_flags || bt->n == 0) return 0;            // (no frames: the lanes are empty)
+    FilterWs &W = P.flt;
+    const uint32_t S = c->n_lanes;
+    if ((rc = ensure_dev(c, (void **)&W.pkt, &W.pkt_cap, ((size_t)o->lane_cap + 1) * 4)) ||
+        (rc = ensure_dev(c, (void **)&W.off, &W.off_cap, ((size_t)S + 1) * 4)))
+        return rc;
+    const udpdk_rx_lanes_t in = {o->meta_dev, bt->n, o->lane_off_dev, o->lane_pkt_dev, o->lane_cap, S};
+    if ((rc = filter_enqueue(c, W, P.stream, &in, c->drop_flags, W.off, W.pkt, o->lane_cap))) return rc;
+    const uint32_t tiles = ceil_div(o->lane_cap, FLT_TILE);
+    hipLaunchKernelGGL(rx_filter_copy, dim3(tiles + ceil_div(S + 1u, (uint32_t)FLT_BLOCK)), dim3(FLT_BLOCK), 0,
+                       P.stream, (const uint32_t *)W.off, (const uint32_t *)W.pkt, (const FilterResult *)W.res,
+                       o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
+    HIPC(c, hipGetLastError());
+    P.filtered = true;
+    return 0;
+}
+
+int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udpdk_rx_out_t *o)
 {
     if (!c || !bt || !o || !c->have_snapshot) return -EINVAL;
     if (bt->n > c->max_frames || bt->frames_bytes >= (1ull << 32)) return -EINVAL;
@@ -818,14 +917,17 @@ int enqueue_result(udpdk_gpu_ctx *c, Pipe &P)
         HIPC(c, hipGetLastError());
     }
     HIPC(c, hipMemcpyAsync(P.h_res, P.res, sizeof(DevResult), hipMemcpyDeviceToHost, P.stream));
+    if (P.filtered)
+        HIPC(c, hipMemcpyAsync(P.flt.h_res, P.flt.res, sizeof(FilterResult), hipMemcpyDeviceToHost, P.stream));
     return 0;
 }
 
 int read_result(Pipe &P, udpdk_rx_stats_t *st)
 {
     for (int k = 0; k < UDPDK_N_COUNTERS; ++k) st->counters[k] = P.h_res->counters[k];
-    st->deliveries = P.h_res->total;
-    st->overflow = st->deliveries > P.last_lane_cap ? 1u : 0u;
+    // (sticky drop mode: the kept count; overflow stays the pre-filter total's)
+    st->deliveries = P.filtered ? P.flt.h_res->kept : P.h_res->total;
+    st->overflow = P.h_res->total > P.last_lane_cap ? 1u : 0u;
     return st->overflow ? -ENOSPC : 0;
 }
 
@@ -948,6 +1050,44 @@ int udpdk_gpu_rx_host(udpdk_gpu_ctx *c, const uint8_t *frames_host, uint64_t fra
         HIPC(c, hipStreamSynchronize(P.stream));
     }
     return rc;
+}
+
+int udpdk_gpu_rx_filter(udpdk_gpu_ctx *c, const udpdk_rx_lanes_t *in, uint32_t flags,
+                        uint32_t *lane_off_out_dev, uint32_t *lane_pkt_out_dev, uint32_t out_cap)
+{
+    if (!c || !in || !lane_off_out_dev || (flags & ~UDPDK_RX_DROP_ALL)) return -EINVAL;
+    if (in->n_lanes == 0 || in->n_lanes > UDPDK_GPU_MAX_LANES || !in->lane_off_dev) return -EINVAL;
+    if ((in->lane_cap && !in->lane_pkt_dev) || (in->n && !in->meta_dev) || (out_cap && !lane_pkt_out_dev))
+        return -EINVAL;
+    HIPC(c, hipSetDevice(c->device));
+    if (c->depth > 1) { int r = join_pipes(c); if (r) return r; }
+    return filter_enqueue(c, c->xflt, c->stream, in, flags, lane_off_out_dev, lane_pkt_out_dev, out_cap);
+}
+
+int udpdk_gpu_rx_drop(udpdk_gpu_ctx *c, int flags)
+{
+    if (!c) return -EINVAL;
+    const int was = (int)c->drop_flags;
+    if (flags < 0) return was;
+    if ((uint32_t)flags & ~UDPDK_RX_DROP_ALL) return -EINVAL;
+    c->drop_flags = (uint32_t)flags;
+    return was;
+}
+
+int udpdk_gpu_rx_drop_stats(udpdk_gpu_ctx *c, udpdk_rx_drop_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    FilterWs *W = c->flt_last;
+    if (!W) return -ENOENT;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipMemcpyAsync(W->h_res, W->res, sizeof(FilterResult), hipMemcpyDeviceToHost, W->stream));
+    HIPC(c, hipStreamSynchronize(W->stream));
+    for (int k = 0; k < 4; ++k) st->dropped[k] = W->h_res->dropped[k];
+    st->kept = W->h_res->kept;
+    st->removed = W->h_res->removed;
+    st->bad_index = W->h_res->bad_index;
+    st->truncated = W->h_res->truncated;
+    return st->kept > W->out_cap ? -ENOSPC : 0;
 }
 
 int udpdk_gpu_rx_host_batch(udpdk_gpu_ctx *c, udpdk_rx_batch_t *batch, const uint32_t **meta_dev)
