@@ -16,9 +16,9 @@ C_SRC     := $(wildcard udpdk_amd/csrc/host/*.c)
 HIP_OBJ   := $(patsubst udpdk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
 C_OBJ     := $(patsubst udpdk_amd/csrc/host/%.c,$(OBJDIR)/host/%.o,$(C_SRC))
 HDRS      := include/udpdk_gpu.h include/udpdk_api.h udpdk_amd/csrc/rx_common.h \
-             udpdk_amd/csrc/rx_plan.h udpdk_amd/csrc/rx_filter.h udpdk_amd/csrc/wave.h udpdk_amd/csrc/stamps.h $(wildcard udpdk_amd/csrc/host/*.h)
+             udpdk_amd/csrc/rx_plan.h udpdk_amd/csrc/rx_filter.h udpdk_amd/csrc/rss_host.h udpdk_amd/csrc/wave.h udpdk_amd/csrc/stamps.h $(wildcard udpdk_amd/csrc/host/*.h)
 
-TOOLS     := tools/bin/bench_sock build/rx_plan_check
+TOOLS     := tools/bin/bench_sock build/rx_plan_check build/rss_host_check
 
 all: $(LIB) oracle $(TOOLS)
 
@@ -47,6 +47,17 @@ tools/bin/bench_sock: tools/bench_sock.c include/udpdk_api.h include/udpdk_gpu.h
 build/rx_plan_check: tools/rx_plan_check.cpp $(HDRS)
 	@mkdir -p build
 	$(HIPCC) -x hip --cuda-host-only -O1 -std=c++17 -Wall -Werror $(INC) $< -o $@
+
+# the host's RSS table builder and per-frame hash behind a main(): host code only, links no project
+# library and runs on a machine without a GPU (tests/test_rss_host.py); rss-asan builds the same
+# program with the address and undefined-behaviour sanitizers (host only, never loaded into Python)
+build/rss_host_check: tools/rss_host_check.c udpdk_amd/csrc/rss_host.h
+	@mkdir -p build
+	$(CC) -O1 -std=gnu11 -Wall -Wextra -Werror $(INC) $< -o $@
+rss-asan: build/rss_host_check_asan
+build/rss_host_check_asan: tools/rss_host_check.c udpdk_amd/csrc/rss_host.h
+	@mkdir -p build
+	$(CC) -O1 -g -std=gnu11 -Wall -Wextra -Werror -fsanitize=address,undefined -fno-sanitize-recover=all $(INC) $< -o $@
 
 # diagnostic library with per-phase s_memtime stamps (tools/stamps.py); never used by tests/bench
 STAMP_LIB := tools/diag/libudpdk_amd.so
@@ -102,4 +113,4 @@ clean:
 	rm -rf build $(LIB) $(TOOLS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean asm stamps pollprof variant FORCE
+.PHONY: all oracle clean asm stamps pollprof variant rss-asan FORCE

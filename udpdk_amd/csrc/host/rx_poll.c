@@ -29,6 +29,7 @@
 #include <time.h>
 
 #include "host_state.h"
+#include "rss_host.h"
 
 /* Diagnostic build (-DUDPDK_POLL_PROFILE): wall time per phase of udpdk_poll_rx, summed over the
  * calls and printed to stderr by udpdk_poll_profile_dump (called from udpdk_cleanup). */
@@ -567,27 +568,14 @@ struct h_sjob {
  * ETH_MQ_RX_RSS with one ring and a "TODO add RSS support", udpdk_init.c:112-137): one RX queue
  * per device, a frame's queue = reta[Toeplitz hash], with udpdk_gpu_rss's hash definition
  * (rx_rss.hip: IPv4 gate as rx_classify, source + destination address, + ports for unfragmented
- * UDP) and its default key and redirection table, by the same 12 x 256 key-window table. Each
- * device then classifies its queue's frames; lanes are merged back in arrival order, so the rings
- * are the single-queue poller's. */
-static uint32_t h_key_window(const uint8_t *key, uint32_t b)   /* key bits [b, b + 32), MSB first */
-{
-    uint64_t w = 0;
-    for (uint32_t i = 0; i < 5; i++) w = (w << 8) | key[(b >> 3) + i];
-    return (uint32_t)(w >> (8u - (b & 7u)));
-}
-
+ * UDP) and its default key and redirection table, by the same 12 x 256 key-window table
+ * (rss_host.h holds both). Each device then classifies its queue's frames; lanes are merged back
+ * in arrival order, so the rings are the single-queue poller's. */
 int h_rss_setup(void)
 {
     udpdk_rss_conf_t conf;
     if (udpdk_gpu_rss_default_conf(&conf, g_udpdk.n_shards)) return -1;
-    for (uint32_t p = 0; p < 12; p++)
-        for (uint32_t v = 0; v < 256; v++) {
-            uint32_t t = 0;
-            for (uint32_t j = 0; j < 8; j++)
-                if (v & (0x80u >> j)) t ^= h_key_window(conf.key, 8u * p + j);
-            g_udpdk.rss_tab[p][v] = t;
-        }
+    rss_key_table(conf.key, g_udpdk.rss_tab);
     memcpy(g_udpdk.rss_reta, conf.reta, sizeof(uint16_t) * conf.reta_size);
     g_udpdk.rss_reta_size = conf.reta_size;
     g_udpdk.rss_types = conf.hash_types;
@@ -601,17 +589,9 @@ static uint32_t h_rss_queue(const struct h_sjob *J, uint32_t i)
     const uint64_t o = J->offset[i];
     const uint32_t len = J->length[i];
     uint32_t hash = 0;
-    if (len >= 34u && o + len <= J->frames_bytes) {
-        const uint8_t *f = J->frames + o;
-        const uint32_t pt = J->ptype ? J->ptype[i] : (f[12] == 0x08 && f[13] == 0x00 ? 0x211u : 0x1u);
-        if (pt & 0x10u) {
-            const uint32_t ff = ((uint32_t)f[20] << 8) | f[21];
-            const int udp4 = !(ff & 0x3FFFu) && f[23] == 17 && len >= 38u && (g_udpdk.rss_types & 2u);
-            if (udp4 || (g_udpdk.rss_types & 1u)) {
-                const uint32_t (*T)[256] = g_udpdk.rss_tab;
-                for (uint32_t b = 0; b < (udp4 ? 12u : 8u); b++) hash ^= T[b][f[26 + b]];
-            }
-        }
+    if (o + len <= J->frames_bytes) {
+        const uint32_t (*T)[256] = g_udpdk.rss_tab;
+        hash = rss_frame_hash(J->frames + o, len, J->ptype ? &J->ptype[i] : NULL, g_udpdk.rss_types, T);
     }
     return g_udpdk.rss_reta[hash & (g_udpdk.rss_reta_size - 1u)];
 }

@@ -20,6 +20,7 @@
 #include "rx_common.h"
 #include "rx_plan.h"
 #include "rx_filter.h"
+#include "rss_host.h"
 
 using namespace udpdk;
 
@@ -155,6 +156,7 @@ struct udpdk_gpu_ctx {
     uint32_t *rss_hist = nullptr, *rss_partial = nullptr, *rss_total = nullptr;
     unsigned long long *rss_fuse = nullptr;   // rss_hash fan-in words (fused queue bases)
     bool rss_no_fuse = false;                 // UDPDK_RSS_FUSE=0 (tests, A/B): the rss_base launch
+    bool rss_trace = false;                   // UDPDK_RSS_TRACE (diagnostic): the form of every call on stderr
 
     // timing
     uint32_t timing_every = 0;                // 0 off, N: events on every Nth call
@@ -1284,24 +1286,14 @@ int udpdk_gpu_rss_config(udpdk_gpu_ctx *c, const udpdk_rss_conf_t *conf)
     {
         const char *e = getenv("UDPDK_RSS_FUSE");
         c->rss_no_fuse = e && atoi(e) == 0;
+        c->rss_trace = getenv("UDPDK_RSS_TRACE") != nullptr;
     }
     HIPC(c, hipMemcpy(c->rss_reta, conf->reta, conf->reta_size * sizeof(uint16_t), hipMemcpyHostToDevice));
-    // Toeplitz key windows per (input byte position, byte value): win(b) = key bits [b, b + 32)
-    // MSB first; the hash of a 12-byte input is the XOR of 12 table entries
+    // Toeplitz key windows per (input byte position, byte value) (rss_host.h): the hash of a
+    // 12-byte input is the XOR of 12 table entries
     {
         std::vector<uint32_t> tab(12 * 256);
-        auto win = [&](uint32_t b) {
-            uint64_t w = 0;
-            for (uint32_t k = 0; k < 5; ++k) w = (w << 8) | conf->key[(b >> 3) + k];
-            return (uint32_t)(w >> (8u - (b & 7u)));
-        };
-        for (uint32_t p = 0; p < 12; ++p)
-            for (uint32_t v = 0; v < 256; ++v) {
-                uint32_t h = 0;
-                for (uint32_t j = 0; j < 8; ++j)
-                    if ((v >> (7u - j)) & 1u) h ^= win(8u * p + j);
-                tab[p * 256 + v] = h;
-            }
+        rss_key_table(conf->key, reinterpret_cast<uint32_t(*)[256]>(tab.data()));
         HIPC(c, hipMemcpy(c->rss_ktab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     RssArgs &r = c->rss;
@@ -1357,6 +1349,8 @@ int udpdk_gpu_rss(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rss_
     a.fuse = fuse ? c->rss_fuse : nullptr;
     a.queue_off = o->queue_off_dev;
     a.total = c->rss_total;
+    if (c->rss_trace)                          // UDPDK_RSS_TRACE: which queue-base form this call takes
+        fprintf(stderr, "rss tiles %u queues %u base %s\n", tiles, S, fuse ? "fused" : a.qmajor ? "one" : "3pass");
     hipLaunchKernelGGL(rss_hash, dim3(tiles), dim3(RSS_BLOCK), 0, st, a);
     HIPC(c, hipGetLastError());
     ScanArgs sa;
