@@ -108,6 +108,25 @@ uint64_t udpdk_rx_nobufs(void);
 int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *out_len,
                    uint32_t max, uint32_t *n_out);
 
+/* One poller turn that answers instead of delivering: the server side of apps/pingpong (recvfrom,
+ * then sendto back to the source) for a whole batch, on the device. The frames (as for
+ * udpdk_poll_rx) are classified on the GPU and every delivery is answered by its own socket with
+ * its own payload, built straight from the received frame's bytes (udpdk_gpu_tx_reply): source
+ * address and port are the socket's binding (the configured IP for an ANY binding), destination
+ * the datagram's source, MTU and UDP checksum as udpdk_tx_drain builds them, and out / out_off /
+ * out_len / *n_out are in udpdk_tx_drain's format (a datagram's fragments are consecutive frames),
+ * replies in lane order: sockets in index order, each socket's datagrams in arrival order. A
+ * delivery to several sockets (address reuse) is answered by each of them. [gpu] rx_drop applies as
+ * in udpdk_poll_rx. The RX rings are not touched and nothing is queued for udpdk_tx_drain. FRAG
+ * frames are counted in stats and not answered. If the replies need more than max frames or
+ * out_cap bytes the call returns -1 with ENOBUFS and *n_out = 0, and may be repeated with more
+ * room. Runs on the main context only. stats may be NULL. Returns 0 or -1 with errno (ENODEV
+ * without a GPU context). */
+int udpdk_poll_echo(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *offset,
+                    const uint16_t *length, const uint32_t *ptype, uint32_t n,
+                    uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *out_len,
+                    uint32_t max, uint32_t *n_out, udpdk_rx_stats_t *stats);
+
 /* Datagrams waiting in the TX rings. */
 uint64_t udpdk_tx_pending(void);
 

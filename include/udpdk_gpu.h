@@ -45,7 +45,9 @@ extern "C" {
  *    udpdk_gpu_rx_gather_packed; TX payloads need UDPDK_GPU_FRAMES_TAILROOM readable bytes
  * 3: udpdk_frag_table_cfg_t grew max_entries (the table's LRU limit) and flags (32 bytes)
  *    (still 3: udpdk_gpu_tx_build_flags / UDPDK_TX_UDP_CKSUM, then udpdk_gpu_rx_filter /
- *    udpdk_gpu_rx_drop / udpdk_gpu_rx_drop_stats were added; a new symbol breaks no caller) */
+ *    udpdk_gpu_rx_drop / udpdk_gpu_rx_drop_stats were added; a new symbol breaks no caller)
+ *    (still 3: udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply / udpdk_gpu_tx_reply_stats /
+ *    udpdk_gpu_tx_reply_geometry were added) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -560,6 +562,77 @@ int udpdk_gpu_tx_build_flags(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg,
                              uint32_t mtu, uint32_t flags);
 /* Output bytes of one datagram of `len` payload bytes and its frame count (host helper). */
 uint64_t udpdk_gpu_tx_span(uint32_t len, uint32_t mtu, uint32_t *n_frames);
+
+/* ---------------------------------------------------------------------------------------------
+ * TX reply: answer received datagrams on the device (the server side of apps/pingpong: recvfrom,
+ * then sendto back to the source; the reference has no batch form of it). Everything tx_build needs
+ * is already in device memory after udpdk_gpu_rx: the payload is at frame byte 42, the peer's
+ * address in frame bytes 26-35 and the answering socket is the lane an entry is in. A reply plan
+ * turns the lane entries [first, first + count) into the descriptor arrays of a udpdk_tx_batch_t
+ * whose payload_dev is the RX batch's frames_dev: no gather, no copy to the host, no host loop. An
+ * application that rewrites payloads in place in the frame buffer between udpdk_gpu_rx and the
+ * reply answers with the rewritten bytes.
+ *
+ * Entry k is lane entry p = first + k, frame i = lane_pkt[p], D = min(lane_off[n_lanes], lane_cap):
+ *   sockfd[k]       the largest lane l < n_lanes with lane_off[l] <= p, an offset beyond D counting
+ *                   as D (udpdk_gpu_rx_filter's bounds convention), so empty lanes are passed over;
+ *                   lane_off must be non-decreasing from lane_off[0] = 0, as an exclusive prefix is
+ *   payload_off[k]  offset[i] + 42
+ *   payload_len[k]  min(length[i] - 42, (dgram_len - 8) & 0xFFFF), dgram_len the big-endian u16 at
+ *                   frame byte 38: udpdk_gpu_rx_gather's rule with an unbounded slot
+ *   dst_ip[k], dst_port[k]   frame bytes 26-29 and 34-35, raw
+ *   frame_off[k]    exclusive prefix of udpdk_gpu_tx_span(payload_len, mtu) over the entries that
+ *                   answer, summed in 64 bits; frame_off[count] = where the output ends (<= out_cap)
+ * An entry does not answer when p >= D, i >= n (bad_index; no descriptor or frame byte is read),
+ * length[i] < 42, offset[i] + length[i] > frames_bytes, its lane is unselected (lane_sel_dev !=
+ * NULL and lane_sel_dev[l] == 0; lane_sel_dev is [n_lanes]), or its frames would end past out_cap
+ * (no_room; the prefix is monotone, so these are a tail of the range and their frame_off is the
+ * output's end). Such an entry gets sockfd -1, zeros in the other arrays and no output bytes;
+ * tx_build writes nothing for a negative sockfd. lanes->meta_dev is not read and may be NULL.
+ *
+ * Both calls are asynchronous on the context stream and join the pipes as udpdk_gpu_tx_build does.
+ * -EINVAL, with nothing enqueued: a NULL pointer (lane_sel_dev excepted), n_lanes outside
+ * 1..UDPDK_GPU_MAX_LANES, frames_bytes or out_cap >= 2^32, a bad mtu (udpdk_gpu_tx_build_mtu's
+ * rule) or flags, frames_out_dev not 16-byte aligned, first + count >= 2^32, no slot table in the
+ * uploaded snapshot, or a snapshot with lane_mask != 0xFFFFFFFF (in compat mode a lane is not a
+ * sockfd). count == 0 returns 0. The plan launches are not event-timed (udpdk_gpu_timing_read).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {                    /* all [count] except frame_off_dev [count + 1] */
+    uint32_t *payload_off_dev; uint16_t *payload_len_dev; int32_t *sockfd_dev;
+    uint32_t *dst_ip_dev; uint16_t *dst_port_dev; uint32_t *frame_off_dev;
+} udpdk_tx_reply_plan_t;
+
+int udpdk_gpu_tx_reply_plan(udpdk_gpu_ctx *ctx, const udpdk_rx_batch_t *batch,
+                            const udpdk_rx_lanes_t *lanes, uint32_t first, uint32_t count,
+                            const uint8_t *lane_sel_dev, uint32_t mtu, uint64_t out_cap,
+                            const udpdk_tx_reply_plan_t *plan);
+/* The plan, then udpdk_gpu_tx_build_flags over {payload_dev = batch->frames_dev, payload_bytes =
+ * batch->frames_bytes, the plan's arrays, n = count} into {frames_out_dev, out_cap,
+ * plan->frame_off_dev}: mtu and flags as there (that launch is timed as always). The output must
+ * not overlap the RX frame buffer. Source address and port are the answering socket's slot (the
+ * config IP for an ANY binding), what a sendto from that socket would send, not the request's
+ * destination. */
+int udpdk_gpu_tx_reply(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg,
+                       const udpdk_rx_batch_t *batch, const udpdk_rx_lanes_t *lanes,
+                       uint32_t first, uint32_t count, const uint8_t *lane_sel_dev, uint32_t mtu,
+                       uint32_t flags, uint8_t *frames_out_dev, uint64_t out_cap,
+                       const udpdk_tx_reply_plan_t *plan);
+
+typedef struct {
+    uint64_t bytes_needed;   /* the out_cap with which no entry is out of room                  */
+    uint32_t replied;        /* entries that answer                                              */
+    uint32_t skipped;        /* count - replied, whatever the reason                             */
+    uint32_t bad_index;      /* entries >= n                                                     */
+    uint32_t unselected;     /* entries with a good frame in an unselected lane                  */
+    uint32_t no_room;        /* entries out of room                                              */
+    uint32_t frames;         /* output frames of the entries that answer, fragments included     */
+} udpdk_tx_reply_stats_t;
+/* Of the last plan on the context (-ENOENT when there was none). Synchronises. -ENOSPC when
+ * no_room > 0. */
+int udpdk_gpu_tx_reply_stats(udpdk_gpu_ctx *ctx, udpdk_tx_reply_stats_t *stats);
+/* Entries per workgroup of the plan kernels and the workgroup count for `count` entries (host
+ * only, like udpdk_gpu_rx_geometry). */
+int udpdk_gpu_tx_reply_geometry(uint32_t count, uint32_t *entries_per_block, uint32_t *n_blocks);
 
 /* ---------------------------------------------------------------------------------------------
  * Timing (for bench.py / the roofline): on every `enable`-th udpdk_gpu_rx call (0 = off, 1 =

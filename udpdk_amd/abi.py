@@ -151,6 +151,19 @@ class TxOut(C.Structure):
                 ("frame_off_dev", C.c_void_p)]
 
 
+class TxReplyPlan(C.Structure):
+    """udpdk_tx_reply_plan_t: all [count] except frame_off_dev [count + 1]."""
+    _fields_ = [("payload_off_dev", C.c_void_p), ("payload_len_dev", C.c_void_p),
+                ("sockfd_dev", C.c_void_p), ("dst_ip_dev", C.c_void_p),
+                ("dst_port_dev", C.c_void_p), ("frame_off_dev", C.c_void_p)]
+
+
+class TxReplyStats(C.Structure):
+    _fields_ = [("bytes_needed", C.c_uint64), ("replied", C.c_uint32), ("skipped", C.c_uint32),
+                ("bad_index", C.c_uint32), ("unselected", C.c_uint32), ("no_room", C.c_uint32),
+                ("frames", C.c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol the headers declare
 _P = C.c_void_p
 _PROTOS = {
@@ -208,6 +221,13 @@ _PROTOS = {
     "udpdk_gpu_tx_build_flags": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(TxBatch),
                                            C.POINTER(TxOut), C.c_uint32, C.c_uint32]),
     "udpdk_gpu_tx_span": (C.c_uint64, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_tx_reply_plan": (C.c_int, [_P, C.POINTER(RxBatch), C.POINTER(RxLanes), C.c_uint32, C.c_uint32,
+                                          _P, C.c_uint32, C.c_uint64, C.POINTER(TxReplyPlan)]),
+    "udpdk_gpu_tx_reply": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(RxBatch), C.POINTER(RxLanes),
+                                     C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64,
+                                     C.POINTER(TxReplyPlan)]),
+    "udpdk_gpu_tx_reply_stats": (C.c_int, [_P, C.POINTER(TxReplyStats)]),
+    "udpdk_gpu_tx_reply_geometry": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "udpdk_gpu_timing_enable": (C.c_int, [_P, C.c_int]),
     "udpdk_gpu_timing_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "udpdk_gpu_rx_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
@@ -226,6 +246,8 @@ _PROTOS = {
     "udpdk_dump_payload": (None, [C.c_char_p, C.c_int]),
     "udpdk_poll_rx": (C.c_int, [_P, C.c_uint64, _P, _P, _P, C.c_uint32, C.POINTER(RxStats)]),
     "udpdk_tx_drain": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "udpdk_poll_echo": (C.c_int, [_P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, C.c_uint32,
+                                  C.POINTER(C.c_uint32), C.POINTER(RxStats)]),
     "udpdk_btable_snapshot": (C.c_int, [C.POINTER(BindSnapshot), C.c_int]),
     "udpdk_gpu_context": (_P, []),
     "udpdk_shard_devices": (C.c_int, [_P, C.c_int]),
@@ -592,6 +614,91 @@ def rx_gather_packed_run(ctx: GpuContext, b: RxDeviceBatch, lane_pkt: DeviceBuff
     return out
 
 
+def tx_reply_geometry(count: int) -> tuple[int, int]:
+    """(entries per workgroup, workgroups) of the reply plan kernels for `count` entries."""
+    e = C.c_uint32()
+    k = C.c_uint32()
+    _check(lib().udpdk_gpu_tx_reply_geometry(count, C.byref(e), C.byref(k)), "udpdk_gpu_tx_reply_geometry")
+    return e.value, k.value
+
+
+def tx_reply_stats(ctx: GpuContext) -> tuple[int, TxReplyStats]:
+    st = TxReplyStats()
+    rc = lib().udpdk_gpu_tx_reply_stats(ctx.handle, C.byref(st))
+    return rc, st
+
+
+PLAN_FIELDS = (("payload_off", np.uint32), ("payload_len", np.uint16), ("sockfd", np.int32),
+               ("dst_ip", np.uint32), ("dst_port", np.uint16), ("frame_off", np.uint32))
+
+
+def _tx_reply(ctx: GpuContext, cfg, b: RxDeviceBatch, lane_off, lane_pkt, first: int, count: int, *,
+              mtu: int, flags: int, out_cap: int, lane_sel, lane_cap, n, n_lanes, pad: int, guard: int,
+              out_ptr):
+    lane_off = np.ascontiguousarray(lane_off, np.uint32)
+    lane_pkt = np.ascontiguousarray(lane_pkt, np.uint32)
+    n_lanes = len(lane_off) - 1 if n_lanes is None else n_lanes
+    lane_cap = len(lane_pkt) if lane_cap is None else lane_cap
+    bufs = [ctx.upload(lane_off), ctx.upload(lane_pkt)]
+    sel = None
+    if lane_sel is not None:
+        sel = ctx.upload(np.ascontiguousarray(lane_sel, np.uint8))
+        bufs.append(sel)
+    # the plan arrays, `pad` elements longer than the call may write, every byte 0xA5
+    arrs = []
+    for name, dt in PLAN_FIELDS:
+        m = count + pad + (1 if name == "frame_off" else 0)
+        arrs.append(ctx.upload(np.full(max(1, m) * np.dtype(dt).itemsize, 0xA5, np.uint8)))
+    out = None
+    if cfg is not None and out_ptr is None:
+        out = ctx.upload(np.full(out_cap + guard, 0xEE, np.uint8))
+    bufs += arrs + ([out] if out is not None else [])
+    try:
+        bt = RxBatch(b.frames.ptr, b.frames_bytes, b.offset.ptr, b.length.ptr,
+                     b.ptype.ptr if b.ptype is not None else None, b.n if n is None else n)
+        lanes = RxLanes(None, bt.n, bufs[0].ptr, bufs[1].ptr, lane_cap, n_lanes)
+        plan = TxReplyPlan(*[a.ptr for a in arrs])
+        selp = C.c_void_p(sel.ptr) if sel is not None else None
+        if cfg is None:
+            rc = lib().udpdk_gpu_tx_reply_plan(ctx.handle, C.byref(bt), C.byref(lanes), first, count, selp,
+                                               mtu, out_cap, C.byref(plan))
+        else:
+            rc = lib().udpdk_gpu_tx_reply(ctx.handle, C.byref(cfg), C.byref(bt), C.byref(lanes), first, count,
+                                          selp, mtu, flags, C.c_void_p(out.ptr if out is not None else out_ptr),
+                                          out_cap, C.byref(plan))
+        ctx.sync()
+        res = {"rc": rc}
+        for (name, dt), a in zip(PLAN_FIELDS, arrs):
+            res[name] = ctx.download(a, dt, count + pad + (1 if name == "frame_off" else 0))
+        if out is not None:
+            res["out"] = ctx.download(out, np.uint8, out_cap + guard)
+        return res
+    finally:
+        for x in bufs:
+            x.free()
+
+
+def tx_reply_plan_run(ctx: GpuContext, b: RxDeviceBatch, lane_off, lane_pkt, first: int, count: int, *,
+                      mtu: int = 0, out_cap: int = 1 << 24, lane_sel=None, lane_cap=None, n=None,
+                      n_lanes=None, pad: int = 8):
+    """udpdk_gpu_tx_reply_plan over host lanes (uploaded whole; lane_cap defaults to len(lane_pkt),
+    n_lanes to len(lane_off) - 1, n to the batch's). Returns a dict: rc of the call and the six plan
+    arrays as downloaded, each `pad` elements longer than the call may write and pre-filled with
+    0xA5 bytes. The snapshot with the slot table must have been uploaded."""
+    return _tx_reply(ctx, None, b, lane_off, lane_pkt, first, count, mtu=mtu, flags=0, out_cap=out_cap,
+                     lane_sel=lane_sel, lane_cap=lane_cap, n=n, n_lanes=n_lanes, pad=pad, guard=0, out_ptr=None)
+
+
+def tx_reply_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, lane_off, lane_pkt, first: int, count: int, *,
+                 mtu: int = 0, flags: int = 0, out_cap: int = 1 << 20, lane_sel=None, lane_cap=None, n=None,
+                 n_lanes=None, pad: int = 8, guard: int = 4096, out_ptr=None):
+    """udpdk_gpu_tx_reply the same way; res["out"] is the output buffer, out_cap + guard bytes
+    pre-filled with 0xEE (out_ptr: a caller's device pointer instead, nothing downloaded)."""
+    return _tx_reply(ctx, cfg, b, lane_off, lane_pkt, first, count, mtu=mtu, flags=flags, out_cap=out_cap,
+                     lane_sel=lane_sel, lane_cap=lane_cap, n=n, n_lanes=n_lanes, pad=pad, guard=guard,
+                     out_ptr=out_ptr)
+
+
 @dataclass
 class DevRef:
     """A device pointer the context owns (no free)."""
@@ -749,6 +856,23 @@ class HostApi:
         if rc != 0:
             raise UdpdkError(f"udpdk_tx_drain errno={self.errno()}")
         return [bytes(out[off[i]:off[i] + ln[i]]) for i in range(n.value)]
+
+    def poll_echo(self, frames: np.ndarray, frames_bytes: int, offset: np.ndarray, length: np.ndarray,
+                  ptype: np.ndarray | None = None, max_frames=4096, cap=1 << 22):
+        """udpdk_poll_echo: (rc, errno, reply frames in order, RxStats, *n_out)."""
+        offset = np.ascontiguousarray(offset, np.uint32)
+        length = np.ascontiguousarray(length, np.uint16)
+        pt = np.ascontiguousarray(ptype, np.uint32) if ptype is not None else None
+        out = np.zeros(max(1, cap), np.uint8)
+        off = np.zeros(max(1, max_frames), np.uint32)
+        ln = np.zeros(max(1, max_frames), np.uint16)
+        n = C.c_uint32(0xFFFFFFFF)
+        st = RxStats()
+        rc = self.L.udpdk_poll_echo(_ptr(frames), frames_bytes, _ptr(offset), _ptr(length),
+                                    _ptr(pt) if pt is not None else None, len(offset), _ptr(out), cap,
+                                    _ptr(off), _ptr(ln), max_frames, C.byref(n), C.byref(st))
+        err = self.errno() if rc != 0 else 0
+        return rc, err, [bytes(out[off[i]:off[i] + ln[i]]) for i in range(n.value if rc == 0 else 0)], st, n.value
 
     def tx_pending(self) -> int:
         return int(self.L.udpdk_tx_pending())

@@ -219,6 +219,10 @@ struct h_state {
     uint64_t  tx_h_cap, tx_d_cap, tx_fr_d_cap;
     struct h_txsel { int32_t s; uint32_t nf; uint64_t foff; } *tx_sel;
     uint64_t  tx_sel_cap;
+    /* udpdk_poll_echo work buffers (rx_echo.c), grow-only: pinned staging of the batch, its device
+     * copy, the device lanes + reply plan, the built replies, the pinned readback of the plan */
+    void     *ec_h, *ec_in_d, *ec_ws_d, *ec_out_d, *ec_rb_h;
+    uint64_t  ec_h_cap, ec_in_d_cap, ec_ws_d_cap, ec_out_d_cap, ec_rb_h_cap;
     /* poller thread (udpdk_port_attach) */
     pthread_t poller;
     atomic_int poller_run;
@@ -264,6 +268,8 @@ void udpdk_poll_profile_dump(void);   /* -DUDPDK_POLL_PROFILE builds: phase time
 int  h_grow_dev(void **p, uint64_t *cap, uint64_t need);
 int  h_grow_dev_on(udpdk_gpu_ctx *g, void **p, uint64_t *cap, uint64_t need);
 int  h_rss_setup(void);
+int  h_rx_drop_apply(void);               /* under g_udpdk.lock */
+void h_rx_drop_count(const udpdk_rx_stats_t *st);
 int  h_grow_host(void **p, uint64_t *cap, uint64_t need);
 
 /* port_udp.c: the UDP test wire */
@@ -272,5 +278,8 @@ void h_wire_close(void);
 
 /* tx_drain.c */
 void h_tx_buffers_free(void);
+
+/* rx_echo.c */
+void h_echo_buffers_free(void);
 
 #endif

@@ -391,6 +391,7 @@ void udpdk_cleanup(void)
     h_tx_reset();
     h_rx_buffers_free();
     h_tx_buffers_free();
+    h_echo_buffers_free();
     h_arenas_free_all();
     g_udpdk.frag_ready = 0;
     h_shards_destroy();

@@ -217,7 +217,7 @@ static int h_desc_disjoint(const uint32_t *offset, const uint16_t *length, uint3
 /* [gpu] rx_drop / udpdk_config_rx_drop: the setting goes to the main context and every shard
  * context before a poll issues RX (compared once per poll; every RX call of the poll, the pass
  * over reassembled datagrams included, runs on one of these contexts). */
-static int h_rx_drop_apply(void)
+int h_rx_drop_apply(void)
 {
     const uint32_t want = g_udpdk.rx_drop;
     if (want == g_udpdk.rx_drop_applied) return 0;
@@ -232,7 +232,7 @@ static int h_rx_drop_apply(void)
 /* What the drop filter removed from one RX result: its counters are classify's (every delivery
  * made) and its deliveries the kept count. (The polls size lane_cap for every delivery, so no
  * input is truncated and the difference is the filter's `removed`.) */
-static void h_rx_drop_count(const udpdk_rx_stats_t *st)
+void h_rx_drop_count(const udpdk_rx_stats_t *st)
 {
     if (g_udpdk.rx_drop_applied && st->counters[UDPDK_C_DELIVERIES] > st->deliveries)
         __atomic_fetch_add(&g_udpdk.rx_dropped, st->counters[UDPDK_C_DELIVERIES] - st->deliveries,

@@ -430,4 +430,46 @@ int  reasm_run(Reasm *r, hipStream_t st, const udpdk_rx_batch_t *bt, const uint3
 // CK: with the UDP checksum (UDPDK_TX_UDP_CKSUM; one wave per group, TxArgs::parts unused)
 template <bool CK> __global__ void tx_build(TxArgs a);
 
+// Reply plan (tx_reply.hip): lane entries [first, first + count) -> the descriptor arrays of a
+// udpdk_tx_batch_t whose payloads are the received frames' own bytes.
+constexpr int      RPL_BLOCK = 256;          // one entry per lane, 4 waves
+constexpr uint32_t RPL_TILE = RPL_BLOCK;     // entries per workgroup (udpdk_gpu_tx_reply_geometry)
+constexpr int      RPL_BASE_BLOCK = 256;     // tx_reply_base: one workgroup, a run of rows per lane
+// per-workgroup row: output bytes, replies, output frames, entries >= n, entries of unselected lanes
+constexpr uint32_t RPL_ROW = 5;
+enum { RPL_R_BYTES = 0, RPL_R_OK = 1, RPL_R_FRAMES = 2, RPL_R_BADIDX = 3, RPL_R_UNSEL = 4 };
+
+// the device image of udpdk_tx_reply_stats_t, and where the output ends (frame_off[count])
+struct ReplyResult {
+    unsigned long long bytes_needed, end;
+    uint32_t replied, skipped, bad_index, unselected, no_room, frames;
+};
+
+struct ReplyArgs {
+    const uint8_t  *frames;
+    const uint32_t *offset;
+    const uint16_t *length;
+    const uint32_t *lane_off;      // [n_lanes + 1]
+    const uint32_t *lane_pkt;      // [min(lane_off[n_lanes], lane_cap)]
+    const uint8_t  *lane_sel;      // [n_lanes] or null: every lane answers
+    uint32_t *payload_off;         // [count]
+    uint16_t *payload_len;         // [count]
+    int32_t  *sockfd;              // [count]
+    uint32_t *dst_ip;              // [count]
+    uint16_t *dst_port;            // [count]
+    uint32_t *frame_off;           // [count + 1]
+    uint32_t *row;                 // [RPL_ROW][n_blocks], field-major (tx_reply_desc)
+    unsigned long long *base;      // [n_blocks] output bytes before the workgroup (tx_reply_base)
+    ReplyResult *res;
+    uint32_t first, count;
+    uint32_t n, n_lanes, lane_cap;
+    uint32_t frames_bytes, rsrc_bytes;
+    uint32_t mtu;
+    uint32_t out_cap;
+    uint32_t n_blocks;             // ceil(count / RPL_TILE)
+};
+__global__ void tx_reply_desc(ReplyArgs a);
+__global__ void tx_reply_base(ReplyArgs a);
+__global__ void tx_reply_place(ReplyArgs a);
+
 } // namespace udpdk

@@ -61,6 +61,15 @@ struct FilterWs {
     uint32_t out_cap = 0;
 };
 
+// Workspace of the reply plan (tx_reply.hip), lazily sized; one per context (the context stream).
+struct ReplyWs {
+    uint32_t *row = nullptr; size_t row_cap = 0;
+    unsigned long long *base = nullptr; size_t base_cap = 0;
+    ReplyResult *res = nullptr; size_t res_cap = 0;
+    ReplyResult *h_res = nullptr; size_t h_res_cap = 0;    // pinned mirror
+    bool ran = false;                                 // a plan was enqueued (udpdk_gpu_tx_reply_stats)
+};
+
 // One RX pipe = a stream and the per-call workspace. With pipelining depth d > 1, consecutive
 // udpdk_gpu_rx calls rotate over d pipes, so one batch's prologue, tail and compaction overlap
 // the other batches' streaming phases (the calls are independent: distinct batches and output
@@ -144,6 +153,7 @@ struct udpdk_gpu_ctx {
     uint32_t drop_flags = 0;                  // udpdk_gpu_rx_drop: UDPDK_RX_DROP_* (0: no stage)
     FilterWs xflt;                            // explicit udpdk_gpu_rx_filter calls
     FilterWs *flt_last = nullptr;             // the last filter run (udpdk_gpu_rx_drop_stats)
+    ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
 
     unsigned long long *dbg = nullptr;        // diagnostic stamp buffer (UDPDK_STAMPS builds)
     Reasm *reasm = nullptr;                   // udpdk_gpu_frag_table_create
@@ -428,6 +438,9 @@ int udpdk_gpu_ctx_destroy(udpdk_gpu_ctx *c)
         for (void *p : pd) if (p) (void)hipFree(p);
         if (W->h_res) (void)hipHostFree(W->h_res);
     }
+    for (void *p : {(void *)c->rpl.row, (void *)c->rpl.base, (void *)c->rpl.res})
+        if (p) (void)hipFree(p);
+    if (c->rpl.h_res) (void)hipHostFree(c->rpl.h_res);
     for (Pipe &P : c->pipes) {
         void *ph[] = {P.st_frames_h, P.st_desc_h};
         for (void *p : ph) if (p) (void)hipHostFree(p);
@@ -1490,6 +1503,136 @@ int udpdk_gpu_tx_build_flags(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
     if (flags & UDPDK_TX_UDP_CKSUM)
         return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<true>, dim3(grid), dim3(TX_BLOCK), ta);
     return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<false>, dim3(grid), dim3(TX_BLOCK), ta);
+}
+
+namespace {
+
+// Argument checks shared by udpdk_gpu_tx_reply_plan and udpdk_gpu_tx_reply: nothing is enqueued
+// unless all pass.
+int reply_check(const udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_lanes_t *lanes,
+                uint32_t first, uint32_t count, uint32_t mtu, uint64_t out_cap,
+                const udpdk_tx_reply_plan_t *pl)
+{
+    if (!c || !bt || !lanes || !pl) return -EINVAL;
+    if (mtu && (mtu < 68u || mtu > 65535u || (mtu - 20u) % 8u)) return -EINVAL;
+    if (lanes->n_lanes == 0 || lanes->n_lanes > UDPDK_GPU_MAX_LANES) return -EINVAL;
+    if (bt->frames_bytes >= (1ull << 32) || out_cap >= (1ull << 32)) return -EINVAL;
+    if ((uint64_t)first + count > 0xFFFFFFFFull) return -EINVAL;
+    if (!bt->frames_dev || !bt->offset_dev || !bt->length_dev || !lanes->lane_off_dev ||
+        !lanes->lane_pkt_dev) return -EINVAL;
+    if (!pl->payload_off_dev || !pl->payload_len_dev || !pl->sockfd_dev || !pl->dst_ip_dev ||
+        !pl->dst_port_dev || !pl->frame_off_dev) return -EINVAL;
+    if (!c->slots || !c->n_slots) return -EINVAL;
+    if (c->lane_mask != 0xFFFFFFFFu) return -EINVAL;      // compat lanes are not sockets
+    return 0;
+}
+
+// The reply plan (tx_reply.hip) on the context stream: descriptors, base, placement.
+int reply_enqueue(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_lanes_t *lanes,
+                  uint32_t first, uint32_t count, const uint8_t *lane_sel_dev, uint32_t mtu,
+                  uint64_t out_cap, const udpdk_tx_reply_plan_t *pl)
+{
+    ReplyWs &W = c->rpl;
+    const uint32_t nb = ceil_div(count, RPL_TILE);
+    int rc;
+    if ((rc = ensure_dev(c, (void **)&W.row, &W.row_cap, (size_t)nb * RPL_ROW * 4)) ||
+        (rc = ensure_dev(c, (void **)&W.base, &W.base_cap, (size_t)nb * 8)) ||
+        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(ReplyResult))) ||
+        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(ReplyResult))))
+        return rc;
+    ReplyArgs ra;
+    ra.frames = bt->frames_dev;
+    ra.offset = bt->offset_dev;
+    ra.length = bt->length_dev;
+    ra.lane_off = lanes->lane_off_dev;
+    ra.lane_pkt = lanes->lane_pkt_dev;
+    ra.lane_sel = lane_sel_dev;
+    ra.payload_off = pl->payload_off_dev;
+    ra.payload_len = pl->payload_len_dev;
+    ra.sockfd = pl->sockfd_dev;
+    ra.dst_ip = pl->dst_ip_dev;
+    ra.dst_port = pl->dst_port_dev;
+    ra.frame_off = pl->frame_off_dev;
+    ra.row = W.row;
+    ra.base = W.base;
+    ra.res = W.res;
+    ra.first = first;
+    ra.count = count;
+    ra.n = bt->n;
+    ra.n_lanes = lanes->n_lanes;
+    ra.lane_cap = lanes->lane_cap;
+    ra.frames_bytes = (uint32_t)bt->frames_bytes;
+    ra.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+    ra.mtu = mtu;
+    ra.out_cap = (uint32_t)out_cap;
+    ra.n_blocks = nb;
+    hipLaunchKernelGGL(tx_reply_desc, dim3(nb), dim3(RPL_BLOCK), 0, c->stream, ra);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(tx_reply_base, dim3(1), dim3(RPL_BASE_BLOCK), 0, c->stream, ra);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(tx_reply_place, dim3((uint32_t)(((uint64_t)count + RPL_TILE) / RPL_TILE)),
+                       dim3(RPL_BLOCK), 0, c->stream, ra);
+    HIPC(c, hipGetLastError());
+    W.ran = true;
+    return 0;
+}
+
+} // namespace
+
+int udpdk_gpu_tx_reply_geometry(uint32_t count, uint32_t *entries_per_block, uint32_t *n_blocks)
+{
+    if (!entries_per_block || !n_blocks) return -EINVAL;
+    *entries_per_block = RPL_TILE;
+    *n_blocks = std::max<uint32_t>(1u, ceil_div(count, RPL_TILE));
+    return 0;
+}
+
+int udpdk_gpu_tx_reply_plan(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_lanes_t *lanes,
+                            uint32_t first, uint32_t count, const uint8_t *lane_sel_dev, uint32_t mtu,
+                            uint64_t out_cap, const udpdk_tx_reply_plan_t *pl)
+{
+    int rc = reply_check(c, bt, lanes, first, count, mtu, out_cap, pl);
+    if (rc || !count) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    if (c->depth > 1 && (rc = join_pipes(c))) return rc;
+    return reply_enqueue(c, bt, lanes, first, count, lane_sel_dev, mtu, out_cap, pl);
+}
+
+int udpdk_gpu_tx_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
+                       const udpdk_rx_lanes_t *lanes, uint32_t first, uint32_t count,
+                       const uint8_t *lane_sel_dev, uint32_t mtu, uint32_t flags,
+                       uint8_t *frames_out_dev, uint64_t out_cap, const udpdk_tx_reply_plan_t *pl)
+{
+    if (!cfg || !frames_out_dev || (flags & ~UDPDK_TX_UDP_CKSUM)) return -EINVAL;
+    int rc = reply_check(c, bt, lanes, first, count, mtu, out_cap, pl);
+    if (rc) return rc;
+    if (((uintptr_t)frames_out_dev & 15u) || ((uintptr_t)bt->frames_dev & 15u)) return -EINVAL;
+    if (!count) return 0;
+    HIPC(c, hipSetDevice(c->device));
+    if (c->depth > 1 && (rc = join_pipes(c))) return rc;
+    if ((rc = reply_enqueue(c, bt, lanes, first, count, lane_sel_dev, mtu, out_cap, pl))) return rc;
+    const udpdk_tx_batch_t tb = {bt->frames_dev, bt->frames_bytes, pl->payload_off_dev, pl->payload_len_dev,
+                                 pl->sockfd_dev, pl->dst_ip_dev, pl->dst_port_dev, count};
+    const udpdk_tx_out_t to = {frames_out_dev, out_cap, pl->frame_off_dev};
+    return udpdk_gpu_tx_build_flags(c, cfg, &tb, &to, mtu, flags);
+}
+
+int udpdk_gpu_tx_reply_stats(udpdk_gpu_ctx *c, udpdk_tx_reply_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    ReplyWs &W = c->rpl;
+    if (!W.ran) return -ENOENT;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipMemcpyAsync(W.h_res, W.res, sizeof(ReplyResult), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    st->bytes_needed = W.h_res->bytes_needed;
+    st->replied = W.h_res->replied;
+    st->skipped = W.h_res->skipped;
+    st->bad_index = W.h_res->bad_index;
+    st->unselected = W.h_res->unselected;
+    st->no_room = W.h_res->no_room;
+    st->frames = W.h_res->frames;
+    return st->no_room ? -ENOSPC : 0;
 }
 
 #ifdef UDPDK_STAMPS
