@@ -209,6 +209,29 @@ int udpdk_config_rx_drop(int flags);
 /* Deliveries removed that way, summed over polls (and their shards and chunks) of the library
  * session, like udpdk_rx_nobufs. */
 uint64_t udpdk_rx_dropped(void);
+/* Datagrams for several SO_REUSEPORT sockets (ini: [gpu] reuseport = fanout | balance).
+ * UDPDK_REUSEPORT_FANOUT (default): every socket bound to the port with SO_REUSEADDR or
+ * SO_REUSEPORT whose address matches gets a clone, as the reference delivers
+ * (udpdk_poller.c:391-403). UDPDK_REUSEPORT_BALANCE: what that code's TODO asks for
+ * (udpdk_poller.c:387-389): of the matching SO_REUSEPORT sockets exactly one gets a unicast
+ * datagram, the same one for every datagram of a flow (the RSS 4-tuple hash scaled to the group,
+ * as Linux's reuseport_select_sock ranks: udpdk_gpu_rx_balance, udpdk_gpu.h); SO_REUSEADDR-only
+ * sockets, limited broadcast and multicast still fan out. udpdk_poll_rx balances on the GPU before
+ * ring admission and payload gather (chunked and sharded polls, RSS dispatch and datagrams
+ * reassembled from fragments included) and udpdk_poll_echo answers a balanced datagram once, from
+ * the chosen socket. One setting for the whole library, applied to every context by the next
+ * poll; the sockets' flags follow bind, close and setsockopt. Returns the mode in force before
+ * the call; a negative argument only reads it; an unknown mode: -1, EINVAL. */
+#define UDPDK_REUSEPORT_FANOUT  0
+#define UDPDK_REUSEPORT_BALANCE 1
+int udpdk_config_reuseport(int mode);
+/* The clones removed that way, summed over the session like udpdk_rx_dropped (which does not
+ * count them). */
+uint64_t udpdk_rx_balanced(void);
+/* The flags a balancing poll uploads: flags[s] = 1 when socket s is bound with SO_REUSEPORT set
+ * (a socket that set only SO_REUSEADDR is not flagged, although the reference's overlapping option
+ * values make getsockopt report SO_REUSEPORT for it), for s < n. Returns how many sockets are flagged (or -EINVAL). Host only, needs no GPU. */
+int udpdk_reuseport_lanes(uint8_t *flags, uint32_t n);
 
 /* Socket slot state (exch_slot_info, udpdk_types.h:40-47) for the GPU TX slot table. */
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots);

@@ -47,7 +47,9 @@ extern "C" {
  *    (still 3: udpdk_gpu_tx_build_flags / UDPDK_TX_UDP_CKSUM, then udpdk_gpu_rx_filter /
  *    udpdk_gpu_rx_drop / udpdk_gpu_rx_drop_stats were added; a new symbol breaks no caller)
  *    (still 3: udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply / udpdk_gpu_tx_reply_stats /
- *    udpdk_gpu_tx_reply_geometry were added) */
+ *    udpdk_gpu_tx_reply_geometry were added)
+ *    (still 3: udpdk_gpu_rx_balance_select / udpdk_gpu_rx_balance / udpdk_gpu_rx_balance_stats /
+ *    udpdk_gpu_rx_balance_rank / udpdk_gpu_rx_removed were added) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -352,6 +354,75 @@ typedef struct {
  * Synchronises. -ENOSPC if kept > out_cap (sticky mode: the call's lane_cap, which cannot
  * happen). The filter launches are not event-timed (udpdk_gpu_timing_read). */
 int udpdk_gpu_rx_drop_stats(udpdk_gpu_ctx *ctx, udpdk_rx_drop_stats_t *stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * RX reuse-port balance: of a frame's deliveries to sockets that set SO_REUSEPORT one stays, chosen
+ * by the frame's flow hash. The reference clones a datagram to every socket bound with
+ * SO_REUSEADDR or SO_REUSEPORT and marks that as unfinished (udpdk_poller.c:387-389: "if dest
+ * unicast and SO_REUSEPORT, should load balance; if dest broadcast and SO_REUSEADDR or
+ * SO_REUSEPORT, should deliver to all"). This optional stage after the lanes are complete is that
+ * rule. Off by default: then udpdk_gpu_rx enqueues what it always did.
+ *
+ * The uploaded snapshot must have lane_mask == 0xFFFFFFFF (a lane is a sockfd, as for
+ * udpdk_gpu_tx_reply). lane_rp[l] != 0 says lane l's socket has SO_REUSEPORT; a sockfd >= n_lanes
+ * counts as unflagged. D = min(lane_off[n_lanes], lane_cap).
+ *   - For a DELIVERED frame i, its deliveries are those of the demux walk (the bindings of the raw
+ *     dst port at frame byte 36 in list order, a match when ip == the raw dst address at byte 30
+ *     or ip == 0, ended by the first match without reuse). G = the deliveries to flagged lanes in
+ *     that order, g = |G| (counted by the walk itself: UDPDK_META_FANOUT saturates at 127 and only
+ *     tells fan-out < 2, which needs no frame read).
+ *   - g <= 1, or the destination is 255.255.255.255 or multicast (first address byte 224-239):
+ *     every delivery stays. (Directed broadcast would need a netmask the stack does not have.)
+ *   - Otherwise deliveries to unflagged lanes stay (SO_REUSEADDR-only sockets still fan out) and of
+ *     G only member udpdk_gpu_rx_balance_rank(hash_i, g) = (uint64(hash_i) * g) >> 32 stays (the
+ *     reciprocal_scale rule Linux's reuseport_select_sock uses).
+ *   - hash_i = hash_dev[i] when the caller gives hashes (a NIC's mbuf.hash.rss, or an earlier
+ *     udpdk_gpu_rss output), else what udpdk_gpu_rss writes for the frame under the context's RSS
+ *     configuration (udpdk_gpu_rss_default_conf when udpdk_gpu_rss_config was never called): the
+ *     4-tuple hash with UDPDK_RSS_NONFRAG_IPV4_UDP, else the 2-tuple hash with UDPDK_RSS_IPV4, else 0.
+ *   - Entry p of lane l with frame i = lane_pkt[p] is removed iff i >= n (bad_index: no meta or
+ *     frame byte of it is read) or lane_rp[l] != 0 and frame i chose a lane other than l.
+ *   - The output is the drop filter's: a stable compaction, lane_off_out[l] = kept entries before
+ *     min(lane_off[l], D), nothing past lane_cap read, nothing past out_cap written.
+ * meta is never rewritten: fan-out and first sockfd stay classify's.
+ * ------------------------------------------------------------------------------------------- */
+/* The balance as an explicit call on any lane set (lanes->meta_dev required; lanes->n ==
+ * batch->n): out of place, async on the context stream. lane_rp_dev is [n_lanes]; hash_dev is [n]
+ * or NULL. An all-zero lane_rp is a valid identity copy (only entries >= n are removed). -EINVAL
+ * with nothing enqueued: a NULL pointer (hash_dev excepted), n_lanes outside
+ * 1..UDPDK_GPU_MAX_LANES, no snapshot uploaded or one with lane_mask != 0xFFFFFFFF, outputs that
+ * overlap the input lanes. The frames buffer keeps the tailroom contract of udpdk_gpu_rx. */
+int udpdk_gpu_rx_balance_select(udpdk_gpu_ctx *ctx, const udpdk_rx_batch_t *batch,
+                                const udpdk_rx_lanes_t *lanes, const uint8_t *lane_rp_dev,
+                                const uint32_t *hash_dev, uint32_t *lane_off_out_dev,
+                                uint32_t *lane_pkt_out_dev, uint32_t out_cap);
+/* Sticky mode: uploads lane_rp_host[n_lanes] (n_lanes <= the context's max_lanes; lanes past it
+ * are unflagged); NULL or n_lanes == 0 turns the stage off (default: no stage is enqueued).
+ * Synchronises the context. Afterwards every udpdk_gpu_rx / udpdk_gpu_rx_host /
+ * udpdk_gpu_rx_host_async / udpdk_gpu_pipe_rx_host call on this context balances its lanes, on the
+ * call's own stream, before anything reads them (pipeline depths 2-4 work as before), with the
+ * hash computed by the stage. With udpdk_gpu_rx_drop flags set as well, the drop filter runs first;
+ * the two commute. A call under a snapshot with lane_mask != 0xFFFFFFFF returns -EINVAL.
+ *   - udpdk_rx_stats_t: counters[] (UDPDK_C_DELIVERIES too) stay classify's; deliveries becomes
+ *     the kept count, so it still equals lane_off[n_lanes]; overflow and -ENOSPC are still decided
+ *     by the pre-stage total against lane_cap: lane_cap must still hold the fan-out total. */
+int udpdk_gpu_rx_balance(udpdk_gpu_ctx *ctx, const uint8_t *lane_rp_host, uint32_t n_lanes);
+
+typedef struct {
+    uint32_t kept, removed;
+    uint32_t balanced;     /* frames for which a choice among >= 2 members was made */
+    uint32_t bad_index;    /* entries >= n: removed, nothing of theirs read */
+    uint32_t truncated;    /* input lane_off[n_lanes] > lane_cap: only the first lane_cap seen */
+} udpdk_rx_balance_stats_t;
+/* Of the last balance run on the context (explicit or sticky; -ENOENT when there was none).
+ * Synchronises. -ENOSPC if kept > out_cap. The launches are not event-timed. */
+int udpdk_gpu_rx_balance_stats(udpdk_gpu_ctx *ctx, udpdk_rx_balance_stats_t *stats);
+/* (uint64(hash) * g) >> 32: the member of a group of g that a flow hash picks. Host only. */
+uint32_t udpdk_gpu_rx_balance_rank(uint32_t hash, uint32_t g);
+/* Poller internals: the lane entries each sticky stage removed in the call whose results were
+ * last written to *stats (-ENOENT when no call's were). */
+int udpdk_gpu_rx_removed(udpdk_gpu_ctx *ctx, const udpdk_rx_stats_t *stats, uint32_t *dropped,
+                         uint32_t *balanced);
 
 /* ---------------------------------------------------------------------------------------------
  * RX payload delivery: the batch form of udpdk_recvfrom (udpdk_syscall.c:401-488) over the lane

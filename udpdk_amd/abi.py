@@ -91,6 +91,16 @@ class RxDropStats(C.Structure):
                 ("bad_index", C.c_uint32), ("truncated", C.c_uint32)]
 
 
+class RxBalanceStats(C.Structure):
+    _fields_ = [("kept", C.c_uint32), ("removed", C.c_uint32), ("balanced", C.c_uint32),
+                ("bad_index", C.c_uint32), ("truncated", C.c_uint32)]
+
+
+BAL_TILE = 1024           # frames per rx_balance_pick workgroup (rx_balance.h)
+BAL_KEEP_ALL = 0xFFFFFFFF
+REUSEPORT_FANOUT, REUSEPORT_BALANCE = 0, 1   # UDPDK_REUSEPORT_*
+
+
 class RxGather(C.Structure):
     _fields_ = [("payload_dev", C.c_void_p), ("slot_bytes", C.c_uint32), ("len_dev", C.c_void_p),
                 ("src_ip_dev", C.c_void_p), ("src_port_dev", C.c_void_p)]
@@ -205,6 +215,12 @@ _PROTOS = {
     "udpdk_gpu_rx_filter": (C.c_int, [_P, C.POINTER(RxLanes), C.c_uint32, _P, _P, C.c_uint32]),
     "udpdk_gpu_rx_drop": (C.c_int, [_P, C.c_int]),
     "udpdk_gpu_rx_drop_stats": (C.c_int, [_P, C.POINTER(RxDropStats)]),
+    "udpdk_gpu_rx_balance_select": (C.c_int, [_P, C.POINTER(RxBatch), C.POINTER(RxLanes), _P, _P, _P, _P,
+                                              C.c_uint32]),
+    "udpdk_gpu_rx_balance": (C.c_int, [_P, _P, C.c_uint32]),
+    "udpdk_gpu_rx_balance_stats": (C.c_int, [_P, C.POINTER(RxBalanceStats)]),
+    "udpdk_gpu_rx_balance_rank": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "udpdk_gpu_rx_removed": (C.c_int, [_P, C.POINTER(RxStats), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "udpdk_gpu_rx_gather": (C.c_int, [_P, C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32,
                                       C.POINTER(RxGather)]),
     "udpdk_gpu_rx_gather_packed": (C.c_int, [_P, C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32, _P,
@@ -259,6 +275,9 @@ _PROTOS = {
     "udpdk_config_tx_cksum": (C.c_int, [C.c_int]),
     "udpdk_config_rx_drop": (C.c_int, [C.c_int]),
     "udpdk_rx_dropped": (C.c_uint64, []),
+    "udpdk_config_reuseport": (C.c_int, [C.c_int]),
+    "udpdk_rx_balanced": (C.c_uint64, []),
+    "udpdk_reuseport_lanes": (C.c_int, [_P, C.c_uint32]),
     "udpdk_tx_pending": (C.c_uint64, []),
     "udpdk_tx_dropped": (C.c_uint64, []),
     "udpdk_rx_nobufs": (C.c_uint64, []),
@@ -440,6 +459,16 @@ class GpuContext:
             _check(rc, "udpdk_gpu_rx_drop")
         return rc
 
+    def rx_balance(self, lane_rp=None):
+        """Sticky reuse-port balance (udpdk_gpu_rx_balance): the lanes' SO_REUSEPORT flags for
+        every later RX call on the context; None turns the stage off."""
+        if lane_rp is None or len(lane_rp) == 0:
+            _check(lib().udpdk_gpu_rx_balance(self.handle, None, 0), "udpdk_gpu_rx_balance")
+            return
+        f = np.ascontiguousarray(lane_rp, np.uint8)
+        _check(lib().udpdk_gpu_rx_balance(self.handle, f.ctypes.data_as(C.c_void_p), len(f)),
+               "udpdk_gpu_rx_balance")
+
     def timing(self, every: int):
         """0 = off, N = record kernel events on every Nth udpdk_gpu_rx call."""
         _check(lib().udpdk_gpu_timing_enable(self.handle, int(every)), "timing_enable")
@@ -553,6 +582,53 @@ def rx_filter_run(ctx: GpuContext, meta: np.ndarray, lane_off: np.ndarray, lane_
     finally:
         for b in bufs:
             b.free()
+
+
+def rx_balance_stats(ctx: GpuContext) -> tuple[int, RxBalanceStats]:
+    st = RxBalanceStats()
+    rc = lib().udpdk_gpu_rx_balance_stats(ctx.handle, C.byref(st))
+    return rc, st
+
+
+def rx_balance_rank(hash32: int, g: int) -> int:
+    return int(lib().udpdk_gpu_rx_balance_rank(hash32, g))
+
+
+def rx_balance_run(ctx: GpuContext, b: RxDeviceBatch, meta: np.ndarray, lane_off: np.ndarray,
+                   lane_pkt: np.ndarray, lane_rp: np.ndarray, *, hashes: np.ndarray | None = None,
+                   n: int | None = None, lane_cap: int | None = None, out_cap: int | None = None,
+                   pad: int = 0, fill: int = 0xA5A5A5A5):
+    """udpdk_gpu_rx_balance_select over host lane arrays and a device batch: upload, run, download;
+    rx_filter_run's conventions. Returns (lane_off_out, lane_pkt_out[out_cap + pad],
+    RxBalanceStats, rc of udpdk_gpu_rx_balance_stats)."""
+    meta = np.ascontiguousarray(meta, np.uint32)
+    lane_off = np.ascontiguousarray(lane_off, np.uint32)
+    lane_pkt = np.ascontiguousarray(lane_pkt, np.uint32)
+    lane_rp = np.ascontiguousarray(lane_rp, np.uint8)
+    n = len(meta) if n is None else n
+    lane_cap = len(lane_pkt) if lane_cap is None else lane_cap
+    out_cap = lane_cap if out_cap is None else out_cap
+    n_lanes = len(lane_off) - 1
+    bufs = [ctx.upload(meta), ctx.upload(lane_off), ctx.upload(lane_pkt), ctx.upload(lane_rp),
+            ctx.upload(np.full(n_lanes + 1, fill, np.uint32)),
+            ctx.upload(np.full(out_cap + pad, fill, np.uint32))]
+    if hashes is not None:
+        bufs.append(ctx.upload(np.ascontiguousarray(hashes, np.uint32)))
+    md, od, pd, rd, oo, po = bufs[:6]
+    try:
+        bt = RxBatch(b.frames.ptr, b.frames_bytes, b.offset.ptr, b.length.ptr,
+                     b.ptype.ptr if b.ptype is not None else None, n)
+        lanes = RxLanes(md.ptr, n, od.ptr, pd.ptr, lane_cap, n_lanes)
+        _check(lib().udpdk_gpu_rx_balance_select(
+            ctx.handle, C.byref(bt), C.byref(lanes), C.c_void_p(rd.ptr),
+            C.c_void_p(bufs[6].ptr) if hashes is not None else None, C.c_void_p(oo.ptr),
+            C.c_void_p(po.ptr), out_cap), "udpdk_gpu_rx_balance_select")
+        rc, st = rx_balance_stats(ctx)
+        return (ctx.download(oo, np.uint32, n_lanes + 1), ctx.download(po, np.uint32, out_cap + pad),
+                st, rc)
+    finally:
+        for x in bufs:
+            x.free()
 
 
 @dataclass
@@ -905,6 +981,21 @@ class HostApi:
 
     def rx_dropped(self) -> int:
         return int(self.L.udpdk_rx_dropped())
+
+    def config_reuseport(self, mode: int) -> int:
+        """How datagrams for several SO_REUSEPORT sockets are delivered (udpdk_config_reuseport,
+        REUSEPORT_FANOUT / REUSEPORT_BALANCE): returns the previous mode; a negative argument only
+        reads it."""
+        return self.L.udpdk_config_reuseport(int(mode))
+
+    def rx_balanced(self) -> int:
+        return int(self.L.udpdk_rx_balanced())
+
+    def reuseport_lanes(self, n: int) -> tuple[int, np.ndarray]:
+        """udpdk_reuseport_lanes: (sockets flagged, flags[n])."""
+        f = np.full(max(1, n), 0xEE, np.uint8)
+        rc = self.L.udpdk_reuseport_lanes(f.ctypes.data_as(C.c_void_p), n)
+        return rc, f[:n]
 
     def snapshot(self, compat: bool = False) -> BindSnapshot:
         snap = BindSnapshot()

@@ -87,9 +87,20 @@ struct h_slot {                  /* exch_slot_info (udpdk_types.h:40-47) + bind 
     /* binding (at most one per socket): node of its port's list */
     int32_t  prev, next;
     uint8_t  reuse_addr, reuse_port;
+    uint8_t  rp_member;          /* bound with every bit of SO_REUSEPORT set (h_slot_balanced)      */
     struct h_ring rx;
     struct h_txq  tx;
 };
+
+/* Whether a balancing poll treats the socket as a member of its port's reuse-port group: bound with
+ * every bit of SO_REUSEPORT set. (The reference's option values overlap, SO_REUSEADDR = 2 inside
+ * SO_REUSEPORT = 15, and its bind path tests `opts & SO_REUSEPORT`, so reuse_port is also set for a
+ * socket that only asked for SO_REUSEADDR: such a socket keeps its clone of every datagram.) Like
+ * reuse_port, fixed by the options in force at bind. */
+static inline uint8_t h_slot_balanced(const struct h_slot *sl)
+{
+    return sl->used && sl->bound && sl->rp_member;
+}
 
 /* Device buffers of one context's payload gather (the gather list + the kernel's outputs). */
 struct h_gbuf {
@@ -144,6 +155,10 @@ struct h_state {
                                     poll sets on every context (udpdk_gpu_rx_drop)                 */
     uint32_t rx_drop_applied;    /* ... and what the contexts hold (fresh contexts: 0)           */
     uint64_t rx_dropped;         /* deliveries removed that way (udpdk_rx_dropped)                */
+    uint32_t reuseport;          /* [gpu] reuseport / udpdk_config_reuseport: UDPDK_REUSEPORT_*     */
+    uint32_t reuseport_applied;  /* ... what the contexts hold (fresh contexts: fanout), and the    */
+    uint64_t reuseport_version;  /* snapshot version their lane flags were built from             */
+    uint64_t rx_balanced;        /* reuse-port clones removed (udpdk_rx_balanced)                  */
     udpdk_gpu_ctx *gpu;
     int      gpu_device;
     uint32_t gpu_max_frames, gpu_max_lanes;
@@ -269,7 +284,8 @@ int  h_grow_dev(void **p, uint64_t *cap, uint64_t need);
 int  h_grow_dev_on(udpdk_gpu_ctx *g, void **p, uint64_t *cap, uint64_t need);
 int  h_rss_setup(void);
 int  h_rx_drop_apply(void);               /* under g_udpdk.lock */
-void h_rx_drop_count(const udpdk_rx_stats_t *st);
+int  h_reuseport_apply(void);             /* under g_udpdk.lock, after h_snapshot_refresh */
+void h_rx_drop_count(udpdk_gpu_ctx *g, const udpdk_rx_stats_t *st);
 int  h_grow_host(void **p, uint64_t *cap, uint64_t need);
 
 /* port_udp.c: the UDP test wire */

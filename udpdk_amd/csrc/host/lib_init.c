@@ -41,6 +41,7 @@ static void h_config_defaults(void)
     g_udpdk.frag_flags = 0;            /* RFC 1071 header checksum on reassembled datagrams */
     g_udpdk.tx_udp_cksum = 0;          /* UDP checksum 0 on TX, udpdk_syscall.c:343 */
     g_udpdk.rx_drop = 0;               /* every delivery reaches its socket, as in the reference */
+    g_udpdk.reuseport = UDPDK_REUSEPORT_FANOUT;   /* every reuse socket gets a clone, as in the reference */
     g_udpdk.arena_bytes_max = 4ull << 30;
     g_udpdk.arena_count_max = 1024;
     g_udpdk.port_spec[0] = g_udpdk.port_peer[0] = 0;
@@ -74,6 +75,7 @@ void udpdk_host_reset(void)
     g_udpdk.mtu = 1500;
     g_udpdk.tx_udp_cksum = 0;
     g_udpdk.rx_drop = 0;
+    g_udpdk.reuseport = UDPDK_REUSEPORT_FANOUT;
     pthread_mutex_unlock(&g_udpdk.lock);
 }
 
@@ -278,6 +280,13 @@ static int h_load_ini(const char *path)
              * takes out of the lanes before ring admission (UDPDK_RX_DROP_*) */
             const int fl = h_parse_rx_drop(v);
             if (fl < 0 || udpdk_config_rx_drop(fl) < 0) { rc = -1; break; }
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "reuseport")) {
+            /* fanout (default): a datagram goes to every SO_REUSEADDR / SO_REUSEPORT socket that
+             * matches, as the reference clones it; balance: of the SO_REUSEPORT sockets one gets
+             * it, chosen by the flow hash (udpdk_gpu_rx_balance) */
+            if (!strcmp(v, "fanout")) udpdk_config_reuseport(UDPDK_REUSEPORT_FANOUT);
+            else if (!strcmp(v, "balance")) udpdk_config_reuseport(UDPDK_REUSEPORT_BALANCE);
+            else { rc = -1; break; }
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port")) {
             snprintf(g_udpdk.port_spec, sizeof(g_udpdk.port_spec), "%s", v);
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port_peer")) {
@@ -309,6 +318,7 @@ int udpdk_init(int argc, char *argv[])
                                   g_udpdk.gpu_max_lanes, &g_udpdk.gpu);
     if (rc) { errno = rc == -ENODEV ? ENODEV : -rc; g_udpdk.gpu = NULL; return -1; }
     g_udpdk.rx_drop_applied = 0;       /* new contexts drop nothing until a poll sets them */
+    g_udpdk.reuseport_applied = UDPDK_REUSEPORT_FANOUT;   /* ... and balance nothing */
     /* [gpu] devices with two or more entries: one RX shard context per entry (SURVEY.md §7 step
      * 8); a poll splits its batch into that many contiguous shards */
     if (g_udpdk.n_shards > 1) {
@@ -423,6 +433,30 @@ int udpdk_config_rx_drop(int flags)
     if (flags >= 0 && ((uint32_t)flags & ~UDPDK_RX_DROP_ALL)) { errno = EINVAL; return -1; }
     if (flags >= 0) g_udpdk.rx_drop = (uint32_t)flags;
     return was;
+}
+
+int udpdk_config_reuseport(int mode)
+{
+    const int was = (int)g_udpdk.reuseport;
+    if (mode > UDPDK_REUSEPORT_BALANCE) { errno = EINVAL; return -1; }
+    if (mode >= 0) g_udpdk.reuseport = (uint32_t)mode;
+    return was;
+}
+
+int udpdk_reuseport_lanes(uint8_t *flags, uint32_t n)
+{
+    if (!flags && n) return -EINVAL;
+    int cnt = 0;
+    pthread_mutex_lock(&g_udpdk.lock);
+    for (uint32_t s = 0; s < UDPDK_MAX_SOCKETS; s++) {
+        const struct h_slot *sl = &g_udpdk.slots[s];
+        const uint8_t f = h_slot_balanced(sl);
+        if (s < n) flags[s] = f;
+        cnt += f;
+    }
+    for (uint32_t s = UDPDK_MAX_SOCKETS; s < n; s++) flags[s] = 0;
+    pthread_mutex_unlock(&g_udpdk.lock);
+    return cnt;
 }
 
 int udpdk_config_set(const uint8_t src_mac[6], const uint8_t dst_mac[6], uint32_t src_ip)

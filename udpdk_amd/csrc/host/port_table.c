@@ -48,6 +48,7 @@ int h_btable_add(int sockfd, uint32_t ip, uint32_t port, int opts)
     struct h_slot *sl = &g_udpdk.slots[sockfd];
     sl->reuse_addr = (opts & H_SO_REUSEADDR) != 0;
     sl->reuse_port = (opts & H_SO_REUSEPORT) != 0;
+    sl->rp_member = (opts & H_SO_REUSEPORT) == H_SO_REUSEPORT;
     sl->ip = ip;
     if (ip == 0) {                               /* INADDR_ANY: list head */
         sl->prev = -1;

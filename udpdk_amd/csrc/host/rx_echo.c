@@ -44,7 +44,7 @@ int udpdk_poll_echo(const uint8_t *frames, uint64_t frames_bytes, const uint32_t
     /* the bind snapshot and the slot table the replies' source addresses come from: refreshed
      * under the table lock, tx_lock taken before anything is built (udpdk_tx_drain's order) */
     pthread_mutex_lock(&g_udpdk.lock);
-    if (h_snapshot_refresh() || h_rx_drop_apply()) {
+    if (h_snapshot_refresh() || h_rx_drop_apply() || h_reuseport_apply()) {
         pthread_mutex_unlock(&g_udpdk.lock);
         return -1;
     }
@@ -104,7 +104,7 @@ int udpdk_poll_echo(const uint8_t *frames, uint64_t frames_bytes, const uint32_t
     rc = udpdk_gpu_tx_reply_stats(g, &rs);
     if (rc && rc != -ENOSPC) { errno = -rc; goto done; }
     if ((rc = udpdk_gpu_rx_stats(g, &st))) { errno = -rc; goto done; }
-    h_rx_drop_count(&st);
+    h_rx_drop_count(g, &st);
     /* nothing has been published anywhere: the caller may come back with more room */
     if (rs.no_room || rs.frames > max || rs.bytes_needed > out_cap) { errno = ENOBUFS; goto done; }
     /* 3. the built bytes and the plan's per-datagram arrays back, then the frame table */

@@ -229,14 +229,55 @@ int h_rx_drop_apply(void)
     return 0;
 }
 
-/* What the drop filter removed from one RX result: its counters are classify's (every delivery
- * made) and its deliveries the kept count. (The polls size lane_cap for every delivery, so no
- * input is truncated and the difference is the filter's `removed`.) */
-void h_rx_drop_count(const udpdk_rx_stats_t *st)
+/* What the drop filter and the reuse-port balance removed from one RX result of context g: its
+ * counters are classify's (every delivery made) and its deliveries the kept count. (The polls size
+ * lane_cap for every delivery, so no input is truncated and the difference is the stages'
+ * `removed`.) With one stage on the difference is that stage's; with both, each counter takes its
+ * own stage's count, so udpdk_rx_dropped never counts balanced clones. */
+void h_rx_drop_count(udpdk_gpu_ctx *g, const udpdk_rx_stats_t *st)
 {
-    if (g_udpdk.rx_drop_applied && st->counters[UDPDK_C_DELIVERIES] > st->deliveries)
-        __atomic_fetch_add(&g_udpdk.rx_dropped, st->counters[UDPDK_C_DELIVERIES] - st->deliveries,
-                           __ATOMIC_RELAXED);
+    if (st->counters[UDPDK_C_DELIVERIES] <= st->deliveries) return;
+    const uint64_t gone = st->counters[UDPDK_C_DELIVERIES] - st->deliveries;
+    const int bal = g_udpdk.reuseport_applied == UDPDK_REUSEPORT_BALANCE;
+    if (g_udpdk.rx_drop_applied && !bal) {
+        __atomic_fetch_add(&g_udpdk.rx_dropped, gone, __ATOMIC_RELAXED);
+    } else if (bal && !g_udpdk.rx_drop_applied) {
+        __atomic_fetch_add(&g_udpdk.rx_balanced, gone, __ATOMIC_RELAXED);
+    } else if (bal) {
+        /* both stages ran: each count from its own stage's result (st is the block context g
+         * wrote the call's results to) */
+        uint32_t d = 0, b = 0;
+        if (udpdk_gpu_rx_removed(g, st, &d, &b)) return;
+        __atomic_fetch_add(&g_udpdk.rx_dropped, d, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&g_udpdk.rx_balanced, b, __ATOMIC_RELAXED);
+    }
+}
+
+/* [gpu] reuseport / udpdk_config_reuseport, as h_rx_drop_apply: under `balance` every context gets
+ * the lanes' SO_REUSEPORT flags (a lane is a socket), again whenever the bind table changed (bind and
+ * close move the snapshot version; a socket's options count as they were at its bind); under `fanout` the stage is off. After
+ * h_snapshot_refresh, g_udpdk.lock held. */
+int h_reuseport_apply(void)
+{
+    const uint32_t want = g_udpdk.reuseport;
+    if (want == g_udpdk.reuseport_applied &&
+        (want == UDPDK_REUSEPORT_FANOUT || g_udpdk.reuseport_version == g_udpdk.snap_version))
+        return 0;
+    static uint8_t flags[UDPDK_MAX_SOCKETS];
+    uint32_t n = 0;
+    if (want == UDPDK_REUSEPORT_BALANCE) {
+        n = g_udpdk.snap_lanes < UDPDK_MAX_SOCKETS ? g_udpdk.snap_lanes : UDPDK_MAX_SOCKETS;
+        for (uint32_t s = 0; s < n; s++) {
+            flags[s] = h_slot_balanced(&g_udpdk.slots[s]);
+        }
+    }
+    int rc = udpdk_gpu_rx_balance(g_udpdk.gpu, n ? flags : NULL, n);
+    for (uint32_t k = 0; !rc && g_udpdk.n_shards > 1 && k < g_udpdk.n_shards; k++)
+        rc = udpdk_gpu_rx_balance(g_udpdk.shard[k].g, n ? flags : NULL, n);
+    if (rc) { errno = -rc; return -1; }
+    g_udpdk.reuseport_applied = want;
+    g_udpdk.reuseport_version = g_udpdk.snap_version;
+    return 0;
 }
 
 static int h_frag_pass(const udpdk_rx_batch_t *staged, const uint32_t *meta_dev, uint64_t nfrag,
@@ -283,7 +324,7 @@ static int h_frag_pass(const udpdk_rx_batch_t *staged, const uint32_t *meta_dev,
     udpdk_rx_out_t o2 = {g_udpdk.dv_meta2, g_udpdk.dv_loff2, g_udpdk.dv_lpkt2, cap};
     udpdk_rx_stats_t st2;
     if ((rc = udpdk_gpu_rx(g, &ro.batch, &o2)) || (rc = udpdk_gpu_rx_stats(g, &st2))) { errno = -rc; return -1; }
-    h_rx_drop_count(&st2);
+    h_rx_drop_count(g, &st2);
     const uint32_t D = st2.deliveries;                 /* with [gpu] rx_drop: the kept ones */
     if (h_grow_host((void **)&g_udpdk.fr_lpkt, &g_udpdk.fr_lpkt_cap, 4ull * D + 4)) return -1;
     if ((rc = udpdk_gpu_d2h(g, g_udpdk.fr_loff, g_udpdk.dv_loff2, 4ull * (lanes + 1))) ||
@@ -830,6 +871,7 @@ static int h_shards_rx(const struct h_sjob *J, uint32_t n, uint32_t lanes, uint3
         st->deliveries += S->st.deliveries;
         st->overflow |= S->st.overflow;
         if (!S->n) continue;
+        h_rx_drop_count(S->g, &S->st);
         if (g_udpdk.dispatch_rss)
             for (uint32_t i = 0; i < S->n; i++) meta[S->idx[i]] = S->meta[i];
         else
@@ -1148,7 +1190,7 @@ static int h_poll_chunked(const uint8_t *frames, uint64_t frames_bytes, const ui
         for (uint32_t v = 0; v < UDPDK_N_COUNTERS; v++) tot.counters[v] += C->st.counters[v];
         tot.deliveries += C->st.deliveries;
         tot.overflow |= C->st.overflow;
-        h_rx_drop_count(&C->st);
+        h_rx_drop_count(g, &C->st);
         udpdk_rx_batch_t staged, rb;
         const uint32_t *meta_dev = NULL;
         if ((rc = udpdk_gpu_pipe_batch(g, h_pipe_of(k), &staged, &meta_dev))) { err = -rc; break; }
@@ -1247,7 +1289,7 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
     struct h_arena *ad = NULL, *af = NULL;
     PROF_T(p0);
     if (h_snapshot_refresh()) goto out;
-    if (h_rx_drop_apply()) goto out;
+    if (h_rx_drop_apply() || h_reuseport_apply()) goto out;
     PROF_T(p1);
     const uint32_t lanes = g_udpdk.snap_lanes, maxfan = g_udpdk.snap_maxfan;
     if (g_udpdk.n_shards <= 1) {
@@ -1273,7 +1315,7 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
                                     cap, &st))) { errno = -rc; goto out; }
         if ((rc = udpdk_gpu_rx_host_batch(g, &staged, &meta_dev))) { errno = -rc; goto out; }
     }
-    h_rx_drop_count(&st);
+    if (!sharded) h_rx_drop_count(g, &st);             /* (shards: counted per shard) */
     PROF_T(p2);
     udpdk_rx_batch_t rb;
     uint32_t nd = 0;

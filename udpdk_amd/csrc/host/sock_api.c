@@ -213,6 +213,7 @@ void h_arenas_free_all(void)
 uint64_t udpdk_rx_nobufs(void) { return __atomic_load_n(&g_udpdk.rx_nobufs, __ATOMIC_RELAXED); }
 
 uint64_t udpdk_rx_dropped(void) { return __atomic_load_n(&g_udpdk.rx_dropped, __ATOMIC_RELAXED); }
+uint64_t udpdk_rx_balanced(void) { return __atomic_load_n(&g_udpdk.rx_balanced, __ATOMIC_RELAXED); }
 
 /* ---- TX rings ----------------------------------------------------------------------------- */
 void h_tx_reset(void)
@@ -263,6 +264,7 @@ void h_sockets_reset(void)
     g_udpdk.tx_dropped = 0;
     __atomic_store_n(&g_udpdk.rx_nobufs, 0, __ATOMIC_RELAXED);   /* per library session */
     __atomic_store_n(&g_udpdk.rx_dropped, 0, __ATOMIC_RELAXED);
+    __atomic_store_n(&g_udpdk.rx_balanced, 0, __ATOMIC_RELAXED);
     g_udpdk.version++;
 }
 

@@ -22,6 +22,7 @@
 
 #include "udpdk_gpu.h"
 #include "rx_common.h"
+#include "rss_toeplitz.h"
 #include "wave.h"
 
 namespace udpdk {
@@ -152,13 +153,7 @@ __global__ void __launch_bounds__(RSS_BLOCK) rss_hash(RssArgs a)
             const bool frag = (ff & 0x3FFFu) != 0u;
             const bool udp4 = !frag && ((w20 >> 24) & 0xFFu) == 17u && len[s] >= 38u && (a.hash_types & 2u);
             if (udp4 || (a.hash_types & 1u)) {
-                const uint32_t sa = src, da = dst, pp = ports;
-                hash = tab[0][sa & 255u] ^ tab[1][(sa >> 8) & 255u] ^ tab[2][(sa >> 16) & 255u] ^
-                       tab[3][sa >> 24] ^ tab[4][da & 255u] ^ tab[5][(da >> 8) & 255u] ^
-                       tab[6][(da >> 16) & 255u] ^ tab[7][da >> 24];
-                if (udp4)
-                    hash ^= tab[8][pp & 255u] ^ tab[9][(pp >> 8) & 255u] ^ tab[10][(pp >> 16) & 255u] ^
-                            tab[11][pp >> 24];
+                hash = rss_toeplitz(tab, src, dst, ports, udp4);
             }
         }
         const uint32_t q = reta[hash & (a.reta_size - 1u)];

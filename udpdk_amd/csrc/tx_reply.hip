@@ -43,6 +43,7 @@
 
 #include "udpdk_gpu.h"
 #include "rx_common.h"
+#include "lane_find.h"
 #include "wave.h"
 
 namespace udpdk {
@@ -60,15 +61,10 @@ __device__ __forceinline__ uint32_t reply_span(uint32_t len, uint32_t mtu, uint3
     return span;
 }
 
-// The largest l in [lo, hi] with min(lane_off[l], D) <= p (lo when there is none).
+// The largest l in [lo, hi] with min(lane_off[l], D) <= p (lo when there is none): lane_find.h
 __device__ __forceinline__ uint32_t reply_lane(const ReplyArgs &a, uint32_t D, uint32_t p, uint32_t lo, uint32_t hi)
 {
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-        if (min(a.lane_off[mid], D) <= p) lo = mid;
-        else hi = mid - 1u;
-    }
-    return lo;
+    return lane_find(a.lane_off, D, p, lo, hi);
 }
 
 __global__ void __launch_bounds__(RPL_BLOCK)

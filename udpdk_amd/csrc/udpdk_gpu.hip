@@ -20,6 +20,7 @@
 #include "rx_common.h"
 #include "rx_plan.h"
 #include "rx_filter.h"
+#include "rx_balance.h"
 #include "rss_host.h"
 
 using namespace udpdk;
@@ -61,6 +62,16 @@ struct FilterWs {
     uint32_t out_cap = 0;
 };
 
+// Workspace of the reuse-port balance stage (rx_balance.hip): the filter's compaction workspace,
+// the frames' choices and the count of balanced frames. One per pipe for the sticky mode
+// (udpdk_gpu_rx_balance) and one for explicit udpdk_gpu_rx_balance_select calls.
+struct BalanceWs {
+    FilterWs f;
+    uint32_t *chosen = nullptr; size_t chosen_cap = 0;
+    uint32_t *cnt = nullptr; size_t cnt_cap = 0;          // frames balanced
+    uint32_t *h_cnt = nullptr; size_t h_cnt_cap = 0;      // pinned mirror
+};
+
 // Workspace of the reply plan (tx_reply.hip), lazily sized; one per context (the context stream).
 struct ReplyWs {
     uint32_t *row = nullptr; size_t row_cap = 0;
@@ -95,6 +106,10 @@ struct Pipe {
     uint32_t last_lane_cap = 0;
     FilterWs flt;                             // sticky drop filter
     bool filtered = false;                    // this pipe's last call ran it
+    BalanceWs bal;                            // sticky reuse-port balance
+    bool balanced = false;                    // this pipe's last call ran it
+    const udpdk_rx_stats_t *stats_of = nullptr;   // the stats block read_result filled last, and what
+    uint32_t n_dropped = 0, n_balanced = 0;       // each stage removed in that call (udpdk_gpu_rx_removed)
     // host-resident batches (udpdk_gpu_rx_host[_async]): staging, lazily sized
     uint8_t *st_frames_d = nullptr; size_t st_frames_dcap = 0;
     uint8_t *st_frames_h = nullptr; size_t st_frames_hcap = 0;
@@ -153,6 +168,12 @@ struct udpdk_gpu_ctx {
     uint32_t drop_flags = 0;                  // udpdk_gpu_rx_drop: UDPDK_RX_DROP_* (0: no stage)
     FilterWs xflt;                            // explicit udpdk_gpu_rx_filter calls
     FilterWs *flt_last = nullptr;             // the last filter run (udpdk_gpu_rx_drop_stats)
+    bool bal_on = false;                      // udpdk_gpu_rx_balance: the sticky balance stage
+    uint8_t *bal_rp = nullptr;                // [max_lanes] its lane flags (zero past what was given)
+    uint32_t *bal_ktab = nullptr;             // key windows of the default RSS configuration (no
+                                              // udpdk_gpu_rss_config on this context)
+    BalanceWs xbal;                           // explicit udpdk_gpu_rx_balance_select calls
+    BalanceWs *bal_last = nullptr;            // the last balance run (udpdk_gpu_rx_balance_stats)
     ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
 
     unsigned long long *dbg = nullptr;        // diagnostic stamp buffer (UDPDK_STAMPS builds)
@@ -438,6 +459,16 @@ int udpdk_gpu_ctx_destroy(udpdk_gpu_ctx *c)
         for (void *p : pd) if (p) (void)hipFree(p);
         if (W->h_res) (void)hipHostFree(W->h_res);
     }
+    BalanceWs *bw[MAX_PIPES + 1] = {&c->xbal};
+    for (int i = 0; i < MAX_PIPES; ++i) bw[i + 1] = &c->pipes[i].bal;
+    for (BalanceWs *W : bw) {
+        void *pd[] = {W->f.mask, W->f.row, W->f.base, W->f.pkt, W->f.off, W->f.res, W->chosen, W->cnt};
+        for (void *p : pd) if (p) (void)hipFree(p);
+        if (W->f.h_res) (void)hipHostFree(W->f.h_res);
+        if (W->h_cnt) (void)hipHostFree(W->h_cnt);
+    }
+    for (void *p : {(void *)c->bal_rp, (void *)c->bal_ktab})
+        if (p) (void)hipFree(p);
     for (void *p : {(void *)c->rpl.row, (void *)c->rpl.base, (void *)c->rpl.res})
         if (p) (void)hipFree(p);
     if (c->rpl.h_res) (void)hipHostFree(c->rpl.h_res);
@@ -695,6 +726,108 @@ int filter_enqueue(udpdk_gpu_ctx *c, FilterWs &W, hipStream_t st, const udpdk_rx
     return 0;
 }
 
+// The key-window table the balance stage hashes with: the context's RSS configuration, or the
+// default one (built on first use) when udpdk_gpu_rss_config was never called.
+int balance_ktab(udpdk_gpu_ctx *c, const uint32_t **ktab, uint32_t *types)
+{
+    if (c->rss_ready) {
+        *ktab = c->rss_ktab;
+        *types = c->rss.hash_types;
+        return 0;
+    }
+    if (!c->bal_ktab) {
+        udpdk_rss_conf_t conf;
+        udpdk_gpu_rss_default_conf(&conf, 1);
+        std::vector<uint32_t> tab(12 * 256);
+        rss_key_table(conf.key, reinterpret_cast<uint32_t(*)[256]>(tab.data()));
+        uint32_t *d = nullptr;
+        HIPC(c, hipMalloc((void **)&d, tab.size() * sizeof(uint32_t)));
+        if (hipMemcpy(d, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            return -EIO;
+        }
+        c->bal_ktab = d;
+    }
+    *ktab = c->bal_ktab;
+    *types = UDPDK_RSS_IPV4 | UDPDK_RSS_NONFRAG_IPV4_UDP;
+    return 0;
+}
+
+// The balance stage (rx_balance.hip) over one lane set on stream st: pick, mark, then the filter's
+// base and write.
+int balance_enqueue(udpdk_gpu_ctx *c, BalanceWs &B, hipStream_t st, const udpdk_rx_batch_t *bt,
+                    const udpdk_rx_lanes_t *in, const uint8_t *lane_rp, const uint32_t *hash_dev,
+                    uint32_t *off_out, uint32_t *pkt_out, uint32_t out_cap)
+{
+    FilterWs &W = B.f;
+    const uint32_t tiles = ceil_div(in->lane_cap, FLT_TILE);
+    const uint32_t *ktab = nullptr;
+    uint32_t types = 0;
+    int rc;
+    if ((rc = balance_ktab(c, &ktab, &types)) ||
+        (rc = ensure_dev(c, (void **)&W.mask, &W.mask_cap, ((size_t)tiles * FLT_CHUNKS + 1) * 8)) ||
+        (rc = ensure_dev(c, (void **)&W.row, &W.row_cap, ((size_t)tiles * FLT_ROW + 1) * 4)) ||
+        (rc = ensure_dev(c, (void **)&W.base, &W.base_cap, ((size_t)tiles + 1) * 4)) ||
+        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(FilterResult))) ||
+        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(FilterResult))) ||
+        (rc = ensure_dev(c, (void **)&B.chosen, &B.chosen_cap, ((size_t)in->n + 1) * 4)) ||
+        (rc = ensure_dev(c, (void **)&B.cnt, &B.cnt_cap, 4)) ||
+        (rc = ensure_host(c, (void **)&B.h_cnt, &B.h_cnt_cap, 4)))
+        return rc;
+    HIPC(c, hipMemsetAsync(B.cnt, 0, 4, st));
+    if (in->n) {
+        BalancePickArgs pa;
+        pa.frames = bt->frames_dev;
+        pa.offset = bt->offset_dev;
+        pa.meta = in->meta_dev;
+        pa.port_tab = c->port_tab;
+        pa.binds = c->binds;
+        pa.lane_rp = lane_rp;
+        pa.hash_in = hash_dev;
+        pa.ktab = ktab;
+        pa.chosen = B.chosen;
+        pa.balanced = B.cnt;
+        pa.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+        pa.n = in->n;
+        pa.n_lanes = in->n_lanes;
+        pa.hash_types = types;
+        hipLaunchKernelGGL(rx_balance_pick, dim3(ceil_div(in->n, BAL_TILE)), dim3(BAL_BLOCK), 0, st, pa);
+        HIPC(c, hipGetLastError());
+    }
+    BalanceMarkArgs ma;
+    FilterArgs &fa = ma.f;
+    fa.meta = in->meta_dev;
+    fa.lane_off = in->lane_off_dev;
+    fa.lane_pkt = in->lane_pkt_dev;
+    fa.lane_off_out = off_out;
+    fa.lane_pkt_out = pkt_out;
+    fa.mask = W.mask;
+    fa.row = W.row;
+    fa.base = W.base;
+    fa.res = W.res;
+    fa.n = in->n;
+    fa.lane_cap = in->lane_cap;
+    fa.n_lanes = in->n_lanes;
+    fa.flags = 0;
+    fa.out_cap = out_cap;
+    fa.n_tiles = tiles;
+    ma.chosen = B.chosen;
+    ma.lane_rp = lane_rp;
+    if (tiles) {
+        hipLaunchKernelGGL(rx_balance_mark, dim3(tiles), dim3(FLT_BLOCK), 0, st, ma);
+        HIPC(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(rx_filter_base, dim3(1), dim3(FLT_BASE_BLOCK), 0, st, fa);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(rx_filter_write, dim3(tiles + ceil_div(in->n_lanes + 1u, (uint32_t)FLT_BLOCK)),
+                       dim3(FLT_BLOCK), 0, st, fa);
+    HIPC(c, hipGetLastError());
+    W.stream = st;
+    W.out_cap = out_cap;
+    c->bal_last = &B;
+    return 0;
+}
+
 int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udpdk_rx_out_t *o);
 
 // One batch's RX on a pipe: the launch sequence that makes the lanes (whichever form it takes),
@@ -706,20 +839,39 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
     if (rc) return rc;
     Pipe &P = c->pipes[pipe];
     P.filtered = false;
-    if (!c->drop_flags || bt->n == 0) return 0;            // (no frames: the lanes are empty)
-    FilterWs &W = P.flt;
+    P.balanced = false;
+    if ((!c->drop_flags && !c->bal_on) || bt->n == 0) return 0;   // (no frames: the lanes are empty)
     const uint32_t S = c->n_lanes;
-    if ((rc = ensure_dev(c, (void **)&W.pkt, &W.pkt_cap, ((size_t)o->lane_cap + 1) * 4)) ||
-        (rc = ensure_dev(c, (void **)&W.off, &W.off_cap, ((size_t)S + 1) * 4)))
-        return rc;
     const udpdk_rx_lanes_t in = {o->meta_dev, bt->n, o->lane_off_dev, o->lane_pkt_dev, o->lane_cap, S};
-    if ((rc = filter_enqueue(c, W, P.stream, &in, c->drop_flags, W.off, W.pkt, o->lane_cap))) return rc;
     const uint32_t tiles = ceil_div(o->lane_cap, FLT_TILE);
-    hipLaunchKernelGGL(rx_filter_copy, dim3(tiles + ceil_div(S + 1u, (uint32_t)FLT_BLOCK)), dim3(FLT_BLOCK), 0,
-                       P.stream, (const uint32_t *)W.off, (const uint32_t *)W.pkt, (const FilterResult *)W.res,
-                       o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
-    HIPC(c, hipGetLastError());
-    P.filtered = true;
+    if (c->drop_flags) {
+        FilterWs &W = P.flt;
+        if ((rc = ensure_dev(c, (void **)&W.pkt, &W.pkt_cap, ((size_t)o->lane_cap + 1) * 4)) ||
+            (rc = ensure_dev(c, (void **)&W.off, &W.off_cap, ((size_t)S + 1) * 4)))
+            return rc;
+        if ((rc = filter_enqueue(c, W, P.stream, &in, c->drop_flags, W.off, W.pkt, o->lane_cap))) return rc;
+        hipLaunchKernelGGL(rx_filter_copy, dim3(tiles + ceil_div(S + 1u, (uint32_t)FLT_BLOCK)), dim3(FLT_BLOCK), 0,
+                           P.stream, (const uint32_t *)W.off, (const uint32_t *)W.pkt, (const FilterResult *)W.res,
+                           o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
+        HIPC(c, hipGetLastError());
+        P.filtered = true;
+    }
+    if (c->bal_on) {
+        // after the drop filter, on what it left (the two commute: one removes every entry of a
+        // frame, the other picks by a hash that does not depend on the lanes)
+        if (c->lane_mask != 0xFFFFFFFFu) return -EINVAL;       // compat mode: a lane is not a sockfd
+        FilterWs &W = P.bal.f;
+        if ((rc = ensure_dev(c, (void **)&W.pkt, &W.pkt_cap, ((size_t)o->lane_cap + 1) * 4)) ||
+            (rc = ensure_dev(c, (void **)&W.off, &W.off_cap, ((size_t)S + 1) * 4)))
+            return rc;
+        if ((rc = balance_enqueue(c, P.bal, P.stream, bt, &in, c->bal_rp, nullptr, W.off, W.pkt, o->lane_cap)))
+            return rc;
+        hipLaunchKernelGGL(rx_filter_copy, dim3(tiles + ceil_div(S + 1u, (uint32_t)FLT_BLOCK)), dim3(FLT_BLOCK), 0,
+                           P.stream, (const uint32_t *)W.off, (const uint32_t *)W.pkt, (const FilterResult *)W.res,
+                           o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
+        HIPC(c, hipGetLastError());
+        P.balanced = true;
+    }
     return 0;
 }
 
@@ -904,7 +1056,7 @@ int udpdk_gpu_rx(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_ou
 
 namespace {
 int enqueue_result(udpdk_gpu_ctx *c, Pipe &P);
-int read_result(Pipe &P, udpdk_rx_stats_t *st);
+int read_result(udpdk_gpu_ctx *c, Pipe &P, udpdk_rx_stats_t *st);
 } // namespace
 
 int udpdk_gpu_rx_stats(udpdk_gpu_ctx *c, udpdk_rx_stats_t *st)
@@ -916,7 +1068,7 @@ int udpdk_gpu_rx_stats(udpdk_gpu_ctx *c, udpdk_rx_stats_t *st)
     int rc = enqueue_result(c, P);
     if (rc) return rc;
     HIPC(c, hipStreamSynchronize(P.stream));
-    return read_result(P, st);
+    return read_result(c, P, st);
 }
 
 namespace {
@@ -934,14 +1086,22 @@ int enqueue_result(udpdk_gpu_ctx *c, Pipe &P)
     HIPC(c, hipMemcpyAsync(P.h_res, P.res, sizeof(DevResult), hipMemcpyDeviceToHost, P.stream));
     if (P.filtered)
         HIPC(c, hipMemcpyAsync(P.flt.h_res, P.flt.res, sizeof(FilterResult), hipMemcpyDeviceToHost, P.stream));
+    if (P.balanced)
+        HIPC(c, hipMemcpyAsync(P.bal.f.h_res, P.bal.f.res, sizeof(FilterResult), hipMemcpyDeviceToHost, P.stream));
     return 0;
 }
 
-int read_result(Pipe &P, udpdk_rx_stats_t *st)
+int read_result(udpdk_gpu_ctx *c, Pipe &P, udpdk_rx_stats_t *st)
 {
     for (int k = 0; k < UDPDK_N_COUNTERS; ++k) st->counters[k] = P.h_res->counters[k];
     // (sticky drop mode: the kept count; overflow stays the pre-filter total's)
-    st->deliveries = P.filtered ? P.flt.h_res->kept : P.h_res->total;
+    // (sticky balance mode: what it kept of that)
+    st->deliveries = P.balanced ? P.bal.f.h_res->kept : P.filtered ? P.flt.h_res->kept : P.h_res->total;
+    for (Pipe &Q : c->pipes)
+        if (Q.stats_of == st) Q.stats_of = nullptr;      // (a stats block reused across pipes)
+    P.stats_of = st;
+    P.n_dropped = P.filtered ? P.flt.h_res->removed : 0u;
+    P.n_balanced = P.balanced ? P.bal.f.h_res->removed : 0u;
     st->overflow = P.h_res->total > P.last_lane_cap ? 1u : 0u;
     return st->overflow ? -ENOSPC : 0;
 }
@@ -953,7 +1113,7 @@ int finish_host(udpdk_gpu_ctx *c, Pipe &P)
     udpdk_rx_stats_t *st = P.host_stats;
     P.host_stats = nullptr;
     HIPC(c, hipStreamSynchronize(P.stream));
-    return read_result(P, st);
+    return read_result(c, P, st);
 }
 
 // One host-resident batch on pipe p, all on the pipe's stream: (pageable input: a host copy
@@ -1103,6 +1263,91 @@ int udpdk_gpu_rx_drop_stats(udpdk_gpu_ctx *c, udpdk_rx_drop_stats_t *st)
     st->bad_index = W->h_res->bad_index;
     st->truncated = W->h_res->truncated;
     return st->kept > W->out_cap ? -ENOSPC : 0;
+}
+
+uint32_t udpdk_gpu_rx_balance_rank(uint32_t hash, uint32_t g)
+{
+    return (uint32_t)(((uint64_t)hash * g) >> 32);
+}
+
+namespace {
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return na && nb && x < y + nb && y < x + na;
+}
+} // namespace
+
+int udpdk_gpu_rx_balance_select(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_lanes_t *in,
+                                const uint8_t *lane_rp_dev, const uint32_t *hash_dev,
+                                uint32_t *lane_off_out_dev, uint32_t *lane_pkt_out_dev, uint32_t out_cap)
+{
+    if (!c || !bt || !in || !lane_rp_dev || !lane_off_out_dev) return -EINVAL;
+    if (in->n_lanes == 0 || in->n_lanes > UDPDK_GPU_MAX_LANES || !in->lane_off_dev || !in->meta_dev) return -EINVAL;
+    if ((in->lane_cap && !in->lane_pkt_dev) || (out_cap && !lane_pkt_out_dev)) return -EINVAL;
+    if (bt->n != in->n || bt->frames_bytes >= (1ull << 32)) return -EINVAL;
+    if (bt->n && (!bt->frames_dev || !bt->offset_dev)) return -EINVAL;
+    if (!c->have_snapshot || c->lane_mask != 0xFFFFFFFFu) return -EINVAL;
+    const size_t offb = ((size_t)in->n_lanes + 1) * 4;
+    if (ranges_overlap(lane_off_out_dev, offb, in->lane_off_dev, offb) ||
+        ranges_overlap(lane_off_out_dev, offb, in->lane_pkt_dev, (size_t)in->lane_cap * 4) ||
+        ranges_overlap(lane_pkt_out_dev, (size_t)out_cap * 4, in->lane_off_dev, offb) ||
+        ranges_overlap(lane_pkt_out_dev, (size_t)out_cap * 4, in->lane_pkt_dev, (size_t)in->lane_cap * 4))
+        return -EINVAL;
+    HIPC(c, hipSetDevice(c->device));
+    if (c->depth > 1) { int r = join_pipes(c); if (r) return r; }
+    return balance_enqueue(c, c->xbal, c->stream, bt, in, lane_rp_dev, hash_dev, lane_off_out_dev,
+                           lane_pkt_out_dev, out_cap);
+}
+
+int udpdk_gpu_rx_balance(udpdk_gpu_ctx *c, const uint8_t *lane_rp_host, uint32_t n_lanes)
+{
+    if (!c || n_lanes > c->max_lanes) return -EINVAL;
+    HIPC(c, hipSetDevice(c->device));
+    { int rc = sync_all(c); if (rc) return rc; }             // (calls in flight read the flags)
+    if (!lane_rp_host || n_lanes == 0) {
+        c->bal_on = false;
+        return 0;
+    }
+    if (!c->bal_rp) HIPC(c, hipMalloc((void **)&c->bal_rp, c->max_lanes));
+    std::vector<uint8_t> rp(c->max_lanes, 0);
+    for (uint32_t l = 0; l < n_lanes; ++l) rp[l] = lane_rp_host[l] ? 1 : 0;
+    HIPC(c, hipMemcpy(c->bal_rp, rp.data(), rp.size(), hipMemcpyHostToDevice));
+    const uint32_t *ktab;
+    uint32_t types;
+    { int rc = balance_ktab(c, &ktab, &types); if (rc) return rc; }   // (built now, not inside a call)
+    c->bal_on = true;
+    return 0;
+}
+
+int udpdk_gpu_rx_balance_stats(udpdk_gpu_ctx *c, udpdk_rx_balance_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    BalanceWs *B = c->bal_last;
+    if (!B) return -ENOENT;
+    FilterWs *W = &B->f;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipMemcpyAsync(W->h_res, W->res, sizeof(FilterResult), hipMemcpyDeviceToHost, W->stream));
+    HIPC(c, hipMemcpyAsync(B->h_cnt, B->cnt, 4, hipMemcpyDeviceToHost, W->stream));
+    HIPC(c, hipStreamSynchronize(W->stream));
+    st->kept = W->h_res->kept;
+    st->removed = W->h_res->removed;
+    st->balanced = *B->h_cnt;
+    st->bad_index = W->h_res->bad_index;
+    st->truncated = W->h_res->truncated;
+    return st->kept > W->out_cap ? -ENOSPC : 0;
+}
+
+int udpdk_gpu_rx_removed(udpdk_gpu_ctx *c, const udpdk_rx_stats_t *stats, uint32_t *dropped, uint32_t *balanced)
+{
+    if (!c || !stats || !dropped || !balanced) return -EINVAL;
+    for (const Pipe &P : c->pipes) {
+        if (P.stats_of != stats) continue;
+        *dropped = P.n_dropped;
+        *balanced = P.n_balanced;
+        return 0;
+    }
+    return -ENOENT;
 }
 
 int udpdk_gpu_rx_host_batch(udpdk_gpu_ctx *c, udpdk_rx_batch_t *batch, const uint32_t **meta_dev)
