@@ -233,6 +233,44 @@ uint64_t udpdk_rx_balanced(void);
  * values make getsockopt report SO_REUSEPORT for it), for s < n. Returns how many sockets are flagged (or -EINVAL). Host only, needs no GPU. */
 int udpdk_reuseport_lanes(uint8_t *flags, uint32_t n);
 
+/* Connected UDP sockets: what POSIX programs expect of connect / send / recv / getpeername /
+ * getsockname and the reference's ten entry points do not have.
+ * udpdk_connect fixes the socket's peer: afterwards udpdk_send (and udpdk_sendto with a NULL
+ * dest_addr) sends to it, and the socket receives only datagrams whose source address and port are
+ * the peer's. The others are removed on the GPU before ring admission and payload gather
+ * (udpdk_gpu_rx_peer, udpdk_gpu.h), in one-piece, chunked and sharded polls, under dispatch = rss,
+ * and for datagrams reassembled from fragments (whose frame carries the first fragment's header);
+ * udpdk_poll_echo answers only the peer's datagrams from a connected socket. No ini key: connect
+ * is the switch, and with no socket connected a poll enqueues what it always did.
+ *   - ENOTSOCK / EBADF as udpdk_sendto gives them; EINVAL for a NULL addr or addrlen <
+ *     sizeof(struct sockaddr_in) (AF_UNSPEC: < sizeof(sa_family_t)); EAFNOSUPPORT for a family other
+ *     than AF_INET or AF_UNSPEC.
+ *   - AF_UNSPEC dissolves the association; a second connect replaces the peer.
+ *   - An unbound socket is auto-bound exactly as udpdk_sendto does it.
+ *   - Datagrams already in the socket's ring stay there; the new peer applies from the next poll
+ *     that starts after udpdk_connect returns.
+ *   - With [gpu] reuseport = balance the flow hash may pick a group member that is connected to
+ *     somebody else: that datagram is removed, not re-steered to another member.
+ * udpdk_close and udpdk_host_reset clear the peer. */
+int udpdk_connect(int s, const struct sockaddr *addr, socklen_t addrlen);
+/* udpdk_sendto to the peer; ENOTCONN when the socket is not connected. (udpdk_sendto with a NULL
+ * dest_addr sends to the peer of a connected socket and fails with EINVAL on an unconnected one;
+ * with an address it sends to that address, connected or not.) */
+ssize_t udpdk_send(int s, const void *buf, size_t len, int flags);
+/* udpdk_recvfrom without the source address. */
+ssize_t udpdk_recv(int s, void *buf, size_t len, int flags);
+/* The peer as a sockaddr_in, truncated to *addrlen, which gets the length written; ENOTCONN when
+ * the socket is not connected, EBADF / ENOTSOCK as above, EINVAL for a NULL argument. */
+int udpdk_getpeername(int s, struct sockaddr *addr, socklen_t *addrlen);
+/* The bound address and raw port the same way; 0.0.0.0:0 for an unbound socket. */
+int udpdk_getsockname(int s, struct sockaddr *addr, socklen_t *addrlen);
+/* Deliveries the peer filter removed, summed over the session like udpdk_rx_dropped (which does not
+ * count them). */
+uint64_t udpdk_rx_refused(void);
+/* The records a poll uploads: peers[s] = socket s's peer (on = 1) or all zero, for s < n. Returns
+ * how many sockets are connected (or -EINVAL). Host only, needs no GPU. */
+int udpdk_peer_lanes(udpdk_peer_t *peers, uint32_t n);
+
 /* Socket slot state (exch_slot_info, udpdk_types.h:40-47) for the GPU TX slot table. */
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots);
 

@@ -49,7 +49,9 @@ extern "C" {
  *    (still 3: udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply / udpdk_gpu_tx_reply_stats /
  *    udpdk_gpu_tx_reply_geometry were added)
  *    (still 3: udpdk_gpu_rx_balance_select / udpdk_gpu_rx_balance / udpdk_gpu_rx_balance_stats /
- *    udpdk_gpu_rx_balance_rank / udpdk_gpu_rx_removed were added) */
+ *    udpdk_gpu_rx_balance_rank / udpdk_gpu_rx_removed were added)
+ *    (still 3: udpdk_gpu_rx_peer_select / udpdk_gpu_rx_peer / udpdk_gpu_rx_peer_stats /
+ *    udpdk_gpu_rx_peer_removed were added) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -423,6 +425,69 @@ uint32_t udpdk_gpu_rx_balance_rank(uint32_t hash, uint32_t g);
  * last written to *stats (-ENOENT when no call's were). */
 int udpdk_gpu_rx_removed(udpdk_gpu_ctx *ctx, const udpdk_rx_stats_t *stats, uint32_t *dropped,
                          uint32_t *balanced);
+
+/* ---------------------------------------------------------------------------------------------
+ * RX peer filter: the lane of a connected socket keeps only its peer's datagrams (udpdk_connect,
+ * udpdk_api.h). The reference has no connect: its socket calls stop at sendto / recvfrom and every
+ * application checks src_addr by hand. This optional stage after the lanes are complete applies
+ * POSIX's rule for a connected UDP socket before anything reads the lanes (ring admission, payload
+ * gather, replies). Off by default: then udpdk_gpu_rx enqueues what it always did.
+ *
+ * The uploaded snapshot must have lane_mask == 0xFFFFFFFF (a lane is a sockfd, as for
+ * udpdk_gpu_tx_reply). peer[l] is lane l's record. D = min(lane_off[n_lanes], lane_cap). Entry p of
+ * lane l with frame i = lane_pkt[p]:
+ *   - i >= n: removed (bad_index); no descriptor or frame byte of it is read.
+ *   - peer[l].on == 0: kept; no descriptor and no frame byte is read for the entry.
+ *   - otherwise length[i] < 42 or offset[i] + length[i] > frames_bytes (summed in 64 bits): removed
+ *     (bad_frame); no frame byte is read.
+ *   - otherwise kept iff the raw u32 at frame bytes 26-29 == peer[l].ip and the raw u16 at frame
+ *     bytes 34-35 == peer[l].port (what udpdk_gpu_rx_gather reports as src_ip / src_port); else
+ *     removed (refused).
+ *   - The rule is per entry: a frame that fans out to a connected and an unconnected lane stays in
+ *     the second whatever its source is.
+ *   - The output is the drop filter's: a stable compaction, lane_off_out[l] = kept entries before
+ *     min(lane_off[l], D), nothing past lane_cap read, nothing past out_cap written.
+ * meta is never read (lanes->meta_dev may be NULL, as for udpdk_gpu_tx_reply_plan) or rewritten.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t ip; uint16_t port; uint16_t on; } udpdk_peer_t;   /* raw ip / port; 8 bytes */
+
+/* The peer filter as an explicit call on any lane set (lanes->n == batch->n): out of place, async
+ * on the context stream. peer_dev is [lanes->n_lanes], 8-byte aligned. An all-off peer table is a
+ * valid identity copy (only entries >= n are removed). -EINVAL with nothing enqueued: a NULL
+ * pointer, n_lanes outside 1..UDPDK_GPU_MAX_LANES, no snapshot uploaded or one with lane_mask !=
+ * 0xFFFFFFFF (in compat mode a lane is not a sockfd), outputs that overlap the input lanes,
+ * lanes->n != batch->n. The frames buffer keeps the tailroom contract of udpdk_gpu_rx. */
+int udpdk_gpu_rx_peer_select(udpdk_gpu_ctx *ctx, const udpdk_rx_batch_t *batch,
+                             const udpdk_rx_lanes_t *lanes, const udpdk_peer_t *peer_dev,
+                             uint32_t *lane_off_out_dev, uint32_t *lane_pkt_out_dev, uint32_t out_cap);
+/* Sticky mode: uploads peer_host[n_lanes] (n_lanes <= the context's max_lanes; lanes past it are
+ * off); NULL, n_lanes == 0 or no record with on != 0 turns the stage off (default: no stage is
+ * enqueued). Synchronises the context. Afterwards every udpdk_gpu_rx / udpdk_gpu_rx_host /
+ * udpdk_gpu_rx_host_async / udpdk_gpu_pipe_rx_host call on this context filters its lanes, on the
+ * call's own stream, before anything reads them (pipeline depths 2-4 work as before). With
+ * udpdk_gpu_rx_drop flags or udpdk_gpu_rx_balance on as well, the drop filter runs first, the
+ * balance second and this stage last; all three are per-entry predicates that do not depend on
+ * what else the lanes hold, so they commute. (With the balance on, the hash may pick a group member
+ * connected to somebody else: that delivery is then removed, not re-steered.) A call under a
+ * snapshot with lane_mask != 0xFFFFFFFF returns -EINVAL.
+ *   - udpdk_rx_stats_t: counters[] (UDPDK_C_DELIVERIES too) stay classify's; deliveries becomes
+ *     the kept count, so it still equals lane_off[n_lanes]; overflow and -ENOSPC are still decided
+ *     by the pre-stage total against lane_cap. */
+int udpdk_gpu_rx_peer(udpdk_gpu_ctx *ctx, const udpdk_peer_t *peer_host, uint32_t n_lanes);
+
+typedef struct {
+    uint32_t kept, removed;
+    uint32_t refused;      /* entries of connected lanes from another source                      */
+    uint32_t bad_frame;    /* ... whose frame is shorter than 42 bytes or out of range: not read  */
+    uint32_t bad_index;    /* entries >= n: removed, nothing of theirs read                       */
+    uint32_t truncated;    /* input lane_off[n_lanes] > lane_cap: only the first lane_cap seen    */
+} udpdk_rx_peer_stats_t;
+/* Of the last peer filter run on the context (explicit or sticky; -ENOENT when there was none).
+ * Synchronises. -ENOSPC if kept > out_cap. The launches are not event-timed. */
+int udpdk_gpu_rx_peer_stats(udpdk_gpu_ctx *ctx, udpdk_rx_peer_stats_t *stats);
+/* Poller internals, the sibling of udpdk_gpu_rx_removed: the lane entries the sticky peer filter
+ * removed in the call whose results were last written to *stats (-ENOENT when no call's were). */
+int udpdk_gpu_rx_peer_removed(udpdk_gpu_ctx *ctx, const udpdk_rx_stats_t *stats, uint32_t *refused);
 
 /* ---------------------------------------------------------------------------------------------
  * RX payload delivery: the batch form of udpdk_recvfrom (udpdk_syscall.c:401-488) over the lane

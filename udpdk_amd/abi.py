@@ -96,6 +96,19 @@ class RxBalanceStats(C.Structure):
                 ("bad_index", C.c_uint32), ("truncated", C.c_uint32)]
 
 
+class Peer(C.Structure):
+    """udpdk_peer_t: a lane's peer record (raw ip / port), 8 bytes."""
+    _fields_ = [("ip", C.c_uint32), ("port", C.c_uint16), ("on", C.c_uint16)]
+
+
+PEER_DTYPE = np.dtype([("ip", "<u4"), ("port", "<u2"), ("on", "<u2")])   # udpdk_peer_t as a numpy record
+
+
+class RxPeerStats(C.Structure):
+    _fields_ = [("kept", C.c_uint32), ("removed", C.c_uint32), ("refused", C.c_uint32),
+                ("bad_frame", C.c_uint32), ("bad_index", C.c_uint32), ("truncated", C.c_uint32)]
+
+
 BAL_TILE = 1024           # frames per rx_balance_pick workgroup (rx_balance.h)
 BAL_KEEP_ALL = 0xFFFFFFFF
 REUSEPORT_FANOUT, REUSEPORT_BALANCE = 0, 1   # UDPDK_REUSEPORT_*
@@ -221,6 +234,10 @@ _PROTOS = {
     "udpdk_gpu_rx_balance_stats": (C.c_int, [_P, C.POINTER(RxBalanceStats)]),
     "udpdk_gpu_rx_balance_rank": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "udpdk_gpu_rx_removed": (C.c_int, [_P, C.POINTER(RxStats), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_rx_peer_select": (C.c_int, [_P, C.POINTER(RxBatch), C.POINTER(RxLanes), _P, _P, _P, C.c_uint32]),
+    "udpdk_gpu_rx_peer": (C.c_int, [_P, _P, C.c_uint32]),
+    "udpdk_gpu_rx_peer_stats": (C.c_int, [_P, C.POINTER(RxPeerStats)]),
+    "udpdk_gpu_rx_peer_removed": (C.c_int, [_P, C.POINTER(RxStats), C.POINTER(C.c_uint32)]),
     "udpdk_gpu_rx_gather": (C.c_int, [_P, C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32,
                                       C.POINTER(RxGather)]),
     "udpdk_gpu_rx_gather_packed": (C.c_int, [_P, C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32, _P,
@@ -259,6 +276,13 @@ _PROTOS = {
     "udpdk_sendto": (C.c_ssize_t, [C.c_int, _P, C.c_size_t, C.c_int, _P, C.c_uint32]),
     "udpdk_recvfrom": (C.c_ssize_t, [C.c_int, _P, C.c_size_t, C.c_int, _P, C.POINTER(C.c_uint32)]),
     "udpdk_close": (C.c_int, [C.c_int]),
+    "udpdk_connect": (C.c_int, [C.c_int, _P, C.c_uint32]),
+    "udpdk_send": (C.c_ssize_t, [C.c_int, _P, C.c_size_t, C.c_int]),
+    "udpdk_recv": (C.c_ssize_t, [C.c_int, _P, C.c_size_t, C.c_int]),
+    "udpdk_getpeername": (C.c_int, [C.c_int, _P, C.POINTER(C.c_uint32)]),
+    "udpdk_getsockname": (C.c_int, [C.c_int, _P, C.POINTER(C.c_uint32)]),
+    "udpdk_rx_refused": (C.c_uint64, []),
+    "udpdk_peer_lanes": (C.c_int, [_P, C.c_uint32]),
     "udpdk_dump_payload": (None, [C.c_char_p, C.c_int]),
     "udpdk_poll_rx": (C.c_int, [_P, C.c_uint64, _P, _P, _P, C.c_uint32, C.POINTER(RxStats)]),
     "udpdk_tx_drain": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
@@ -469,6 +493,15 @@ class GpuContext:
         _check(lib().udpdk_gpu_rx_balance(self.handle, f.ctypes.data_as(C.c_void_p), len(f)),
                "udpdk_gpu_rx_balance")
 
+    def rx_peer(self, peers=None):
+        """Sticky peer filter (udpdk_gpu_rx_peer): the lanes' peer records (PEER_DTYPE) for every
+        later RX call on the context; None turns the stage off."""
+        if peers is None or len(peers) == 0:
+            _check(lib().udpdk_gpu_rx_peer(self.handle, None, 0), "udpdk_gpu_rx_peer")
+            return
+        t = np.ascontiguousarray(peers, PEER_DTYPE)
+        _check(lib().udpdk_gpu_rx_peer(self.handle, t.ctypes.data_as(C.c_void_p), len(t)), "udpdk_gpu_rx_peer")
+
     def timing(self, every: int):
         """0 = off, N = record kernel events on every Nth udpdk_gpu_rx call."""
         _check(lib().udpdk_gpu_timing_enable(self.handle, int(every)), "timing_enable")
@@ -624,6 +657,44 @@ def rx_balance_run(ctx: GpuContext, b: RxDeviceBatch, meta: np.ndarray, lane_off
             C.c_void_p(bufs[6].ptr) if hashes is not None else None, C.c_void_p(oo.ptr),
             C.c_void_p(po.ptr), out_cap), "udpdk_gpu_rx_balance_select")
         rc, st = rx_balance_stats(ctx)
+        return (ctx.download(oo, np.uint32, n_lanes + 1), ctx.download(po, np.uint32, out_cap + pad),
+                st, rc)
+    finally:
+        for x in bufs:
+            x.free()
+
+
+def rx_peer_stats(ctx: GpuContext) -> tuple[int, RxPeerStats]:
+    st = RxPeerStats()
+    rc = lib().udpdk_gpu_rx_peer_stats(ctx.handle, C.byref(st))
+    return rc, st
+
+
+def rx_peer_run(ctx: GpuContext, b: RxDeviceBatch, lane_off: np.ndarray, lane_pkt: np.ndarray,
+                peers: np.ndarray, *, n: int | None = None, lane_cap: int | None = None,
+                out_cap: int | None = None, pad: int = 0, fill: int = 0xA5A5A5A5):
+    """udpdk_gpu_rx_peer_select over host lane arrays and a device batch: upload, run, download;
+    rx_filter_run's conventions (no verdict words: the stage reads none). Returns (lane_off_out,
+    lane_pkt_out[out_cap + pad], RxPeerStats, rc of udpdk_gpu_rx_peer_stats)."""
+    lane_off = np.ascontiguousarray(lane_off, np.uint32)
+    lane_pkt = np.ascontiguousarray(lane_pkt, np.uint32)
+    peers = np.ascontiguousarray(peers, PEER_DTYPE)
+    n = b.n if n is None else n
+    lane_cap = len(lane_pkt) if lane_cap is None else lane_cap
+    out_cap = lane_cap if out_cap is None else out_cap
+    n_lanes = len(lane_off) - 1
+    bufs = [ctx.upload(lane_off), ctx.upload(lane_pkt), ctx.upload(peers.view(np.uint8)),
+            ctx.upload(np.full(n_lanes + 1, fill, np.uint32)),
+            ctx.upload(np.full(out_cap + pad, fill, np.uint32))]
+    od, pd, rd, oo, po = bufs
+    try:
+        bt = RxBatch(b.frames.ptr, b.frames_bytes, b.offset.ptr, b.length.ptr,
+                     b.ptype.ptr if b.ptype is not None else None, n)
+        lanes = RxLanes(None, n, od.ptr, pd.ptr, lane_cap, n_lanes)
+        _check(lib().udpdk_gpu_rx_peer_select(ctx.handle, C.byref(bt), C.byref(lanes), C.c_void_p(rd.ptr),
+                                              C.c_void_p(oo.ptr), C.c_void_p(po.ptr), out_cap),
+               "udpdk_gpu_rx_peer_select")
+        rc, st = rx_peer_stats(ctx)
         return (ctx.download(oo, np.uint32, n_lanes + 1), ctx.download(po, np.uint32, out_cap + pad),
                 st, rc)
     finally:
@@ -921,6 +992,53 @@ class HostApi:
         port = struct.unpack(">H", a.raw[2:4])[0]
         ip = socket.inet_ntoa(a.raw[4:8])
         return n, buf.raw[:n], (ip, port)
+
+    def connect(self, s, ip: str | int, port_host: int, addrlen: int = 16, family: int | None = None) -> int:
+        """udpdk_connect; family=socket.AF_UNSPEC dissolves the association."""
+        raw = sockaddr_in(ip, port_host)
+        if family is not None:
+            raw = struct.pack("<H", family) + raw[2:]
+        a = C.create_string_buffer(raw, 16)
+        return self.L.udpdk_connect(s, a, addrlen)
+
+    def send(self, s, payload: bytes, flags: int = 0) -> int:
+        buf = C.create_string_buffer(payload, max(1, len(payload)))
+        return self.L.udpdk_send(s, buf, len(payload), flags)
+
+    def sendto_null(self, s, payload: bytes, flags: int = 0) -> int:
+        """udpdk_sendto with a NULL dest_addr (a connected socket's peer)."""
+        buf = C.create_string_buffer(payload, max(1, len(payload)))
+        return self.L.udpdk_sendto(s, buf, len(payload), flags, None, 0)
+
+    def recv(self, s, maxlen: int = 2048):
+        buf = C.create_string_buffer(maxlen)
+        n = self.L.udpdk_recv(s, buf, maxlen, 0)
+        return (n, None) if n < 0 else (n, buf.raw[:n])
+
+    def _name(self, fn, s, addrlen: int):
+        a = C.create_string_buffer(b"\xEE" * 16, 16)
+        al = C.c_uint32(addrlen)
+        rc = fn(s, a, C.byref(al))
+        if rc != 0:
+            return rc, None, al.value
+        return rc, (socket.inet_ntoa(a.raw[4:8]), struct.unpack(">H", a.raw[2:4])[0]), al.value
+
+    def getpeername(self, s, addrlen: int = 16):
+        """(rc, (ip, port in host order) or None, the length written)."""
+        return self._name(self.L.udpdk_getpeername, s, addrlen)
+
+    def getsockname(self, s, addrlen: int = 16):
+        return self._name(self.L.udpdk_getsockname, s, addrlen)
+
+    def rx_refused(self) -> int:
+        return int(self.L.udpdk_rx_refused())
+
+    def peer_lanes(self, n: int) -> tuple[int, np.ndarray]:
+        """udpdk_peer_lanes: (sockets connected, records[n] as PEER_DTYPE)."""
+        t = np.zeros(max(1, n), PEER_DTYPE)
+        t["ip"] = 0xEEEEEEEE
+        rc = self.L.udpdk_peer_lanes(t.ctypes.data_as(C.c_void_p), n)
+        return rc, t[:n]
 
     def tx_drain(self, max_frames=4096, cap=1 << 22):
         """Frames built on the GPU from the queued sends (needs udpdk_init)."""

@@ -88,6 +88,9 @@ struct h_slot {                  /* exch_slot_info (udpdk_types.h:40-47) + bind 
     int32_t  prev, next;
     uint8_t  reuse_addr, reuse_port;
     uint8_t  rp_member;          /* bound with every bit of SO_REUSEPORT set (h_slot_balanced)      */
+    uint8_t  connected;          /* udpdk_connect: the socket has a peer (always bound then)        */
+    uint16_t peer_port;          /* raw */
+    uint32_t peer_ip;            /* raw */
     struct h_ring rx;
     struct h_txq  tx;
 };
@@ -159,6 +162,11 @@ struct h_state {
     uint32_t reuseport_applied;  /* ... what the contexts hold (fresh contexts: fanout), and the    */
     uint64_t reuseport_version;  /* snapshot version their lane flags were built from             */
     uint64_t rx_balanced;        /* reuse-port clones removed (udpdk_rx_balanced)                  */
+    uint32_t n_connected;        /* sockets with a peer (udpdk_connect)                             */
+    uint32_t peer_applied;       /* the contexts hold a peer table (fresh contexts: none), built    */
+    uint64_t peer_version;       /* ... moves with every change of a socket's peer                  */
+    uint64_t peer_version_applied, peer_snap_version;   /* from these versions of peers and snapshot */
+    uint64_t rx_refused;         /* deliveries the peer filter removed (udpdk_rx_refused)           */
     udpdk_gpu_ctx *gpu;
     int      gpu_device;
     uint32_t gpu_max_frames, gpu_max_lanes;
@@ -285,6 +293,7 @@ int  h_grow_dev_on(udpdk_gpu_ctx *g, void **p, uint64_t *cap, uint64_t need);
 int  h_rss_setup(void);
 int  h_rx_drop_apply(void);               /* under g_udpdk.lock */
 int  h_reuseport_apply(void);             /* under g_udpdk.lock, after h_snapshot_refresh */
+int  h_peer_apply(void);                  /* under g_udpdk.lock, after h_snapshot_refresh */
 void h_rx_drop_count(udpdk_gpu_ctx *g, const udpdk_rx_stats_t *st);
 int  h_grow_host(void **p, uint64_t *cap, uint64_t need);
 

@@ -319,6 +319,7 @@ int udpdk_init(int argc, char *argv[])
     if (rc) { errno = rc == -ENODEV ? ENODEV : -rc; g_udpdk.gpu = NULL; return -1; }
     g_udpdk.rx_drop_applied = 0;       /* new contexts drop nothing until a poll sets them */
     g_udpdk.reuseport_applied = UDPDK_REUSEPORT_FANOUT;   /* ... and balance nothing */
+    g_udpdk.peer_applied = 0;          /* ... and hold no peer table */
     /* [gpu] devices with two or more entries: one RX shard context per entry (SURVEY.md §7 step
      * 8); a poll splits its batch into that many contiguous shards */
     if (g_udpdk.n_shards > 1) {

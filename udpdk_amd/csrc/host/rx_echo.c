@@ -3,7 +3,8 @@
  * side of apps/pingpong, recvfrom + sendto back to the source, for a whole batch on the device).
  *
  * The frames and their descriptors go to the GPU in one pinned H2D; udpdk_gpu_rx makes the lanes
- * ([gpu] rx_drop applies through the context's sticky flags, as in udpdk_poll_rx);
+ * ([gpu] rx_drop, [gpu] reuseport and the peers of connected sockets apply through the context's
+ * sticky stages, as in udpdk_poll_rx);
  * udpdk_gpu_tx_reply turns every lane entry into a reply built straight from the received frame's
  * bytes (headers from the slot table of the uploaded snapshot, the library's MACs, source IP, MTU
  * and tx_udp_cksum); the built bytes and the plan's payload_len / sockfd / frame_off come back and
@@ -44,7 +45,7 @@ int udpdk_poll_echo(const uint8_t *frames, uint64_t frames_bytes, const uint32_t
     /* the bind snapshot and the slot table the replies' source addresses come from: refreshed
      * under the table lock, tx_lock taken before anything is built (udpdk_tx_drain's order) */
     pthread_mutex_lock(&g_udpdk.lock);
-    if (h_snapshot_refresh() || h_rx_drop_apply() || h_reuseport_apply()) {
+    if (h_snapshot_refresh() || h_rx_drop_apply() || h_reuseport_apply() || h_peer_apply()) {
         pthread_mutex_unlock(&g_udpdk.lock);
         return -1;
     }

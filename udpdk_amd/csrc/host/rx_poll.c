@@ -229,28 +229,65 @@ int h_rx_drop_apply(void)
     return 0;
 }
 
-/* What the drop filter and the reuse-port balance removed from one RX result of context g: its
- * counters are classify's (every delivery made) and its deliveries the kept count. (The polls size
- * lane_cap for every delivery, so no input is truncated and the difference is the stages'
- * `removed`.) With one stage on the difference is that stage's; with both, each counter takes its
- * own stage's count, so udpdk_rx_dropped never counts balanced clones. */
+/* What the drop filter, the reuse-port balance and the peer filter removed from one RX result of
+ * context g: its counters are classify's (every delivery made) and its deliveries the kept count.
+ * (The polls size lane_cap for every delivery, so no input is truncated and the difference is the
+ * stages' `removed`.) With one stage on the difference is that stage's; with several, each counter
+ * takes its own stage's count, so udpdk_rx_dropped never counts balanced clones or refused
+ * datagrams. */
 void h_rx_drop_count(udpdk_gpu_ctx *g, const udpdk_rx_stats_t *st)
 {
     if (st->counters[UDPDK_C_DELIVERIES] <= st->deliveries) return;
     const uint64_t gone = st->counters[UDPDK_C_DELIVERIES] - st->deliveries;
+    const int drop = g_udpdk.rx_drop_applied != 0;
     const int bal = g_udpdk.reuseport_applied == UDPDK_REUSEPORT_BALANCE;
-    if (g_udpdk.rx_drop_applied && !bal) {
-        __atomic_fetch_add(&g_udpdk.rx_dropped, gone, __ATOMIC_RELAXED);
-    } else if (bal && !g_udpdk.rx_drop_applied) {
-        __atomic_fetch_add(&g_udpdk.rx_balanced, gone, __ATOMIC_RELAXED);
-    } else if (bal) {
-        /* both stages ran: each count from its own stage's result (st is the block context g
+    const int peer = g_udpdk.peer_applied != 0;
+    if (drop + bal + peer == 1) {
+        __atomic_fetch_add(drop ? &g_udpdk.rx_dropped : bal ? &g_udpdk.rx_balanced : &g_udpdk.rx_refused, gone,
+                           __ATOMIC_RELAXED);
+    } else if (drop + bal + peer > 1) {
+        /* several stages ran: each count from its own stage's result (st is the block context g
          * wrote the call's results to) */
-        uint32_t d = 0, b = 0;
-        if (udpdk_gpu_rx_removed(g, st, &d, &b)) return;
+        uint32_t d = 0, b = 0, r = 0;
+        if (udpdk_gpu_rx_removed(g, st, &d, &b) || udpdk_gpu_rx_peer_removed(g, st, &r)) return;
         __atomic_fetch_add(&g_udpdk.rx_dropped, d, __ATOMIC_RELAXED);
         __atomic_fetch_add(&g_udpdk.rx_balanced, b, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&g_udpdk.rx_refused, r, __ATOMIC_RELAXED);
     }
+}
+
+/* udpdk_connect, as h_reuseport_apply: while any socket is connected every context holds the
+ * lanes' peer records (a lane is a socket), uploaded again whenever a peer or the bind table
+ * changed; when the last association goes the stage is turned off. After h_snapshot_refresh,
+ * g_udpdk.lock held. */
+int h_peer_apply(void)
+{
+    const uint32_t want = g_udpdk.n_connected != 0;
+    if (!want && !g_udpdk.peer_applied) return 0;
+    if (want && g_udpdk.peer_applied && g_udpdk.peer_version_applied == g_udpdk.peer_version &&
+        g_udpdk.peer_snap_version == g_udpdk.snap_version)
+        return 0;
+    static udpdk_peer_t peers[UDPDK_MAX_SOCKETS];
+    uint32_t n = 0, on = 0;
+    if (want) {
+        n = g_udpdk.snap_lanes < UDPDK_MAX_SOCKETS ? g_udpdk.snap_lanes : UDPDK_MAX_SOCKETS;
+        for (uint32_t s = 0; s < n; s++) {
+            const struct h_slot *sl = &g_udpdk.slots[s];
+            const int c = sl->used && sl->connected;
+            peers[s].ip = c ? sl->peer_ip : 0u;
+            peers[s].port = c ? sl->peer_port : 0u;
+            peers[s].on = (uint16_t)c;
+            on += (uint32_t)c;
+        }
+    }
+    int rc = udpdk_gpu_rx_peer(g_udpdk.gpu, n ? peers : NULL, n);
+    for (uint32_t k = 0; !rc && g_udpdk.n_shards > 1 && k < g_udpdk.n_shards; k++)
+        rc = udpdk_gpu_rx_peer(g_udpdk.shard[k].g, n ? peers : NULL, n);
+    if (rc) { errno = -rc; return -1; }
+    g_udpdk.peer_applied = on != 0;
+    g_udpdk.peer_version_applied = g_udpdk.peer_version;
+    g_udpdk.peer_snap_version = g_udpdk.snap_version;
+    return 0;
 }
 
 /* [gpu] reuseport / udpdk_config_reuseport, as h_rx_drop_apply: under `balance` every context gets
@@ -1289,7 +1326,7 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
     struct h_arena *ad = NULL, *af = NULL;
     PROF_T(p0);
     if (h_snapshot_refresh()) goto out;
-    if (h_rx_drop_apply() || h_reuseport_apply()) goto out;
+    if (h_rx_drop_apply() || h_reuseport_apply() || h_peer_apply()) goto out;
     PROF_T(p1);
     const uint32_t lanes = g_udpdk.snap_lanes, maxfan = g_udpdk.snap_maxfan;
     if (g_udpdk.n_shards <= 1) {

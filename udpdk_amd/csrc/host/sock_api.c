@@ -214,6 +214,7 @@ uint64_t udpdk_rx_nobufs(void) { return __atomic_load_n(&g_udpdk.rx_nobufs, __AT
 
 uint64_t udpdk_rx_dropped(void) { return __atomic_load_n(&g_udpdk.rx_dropped, __ATOMIC_RELAXED); }
 uint64_t udpdk_rx_balanced(void) { return __atomic_load_n(&g_udpdk.rx_balanced, __ATOMIC_RELAXED); }
+uint64_t udpdk_rx_refused(void) { return __atomic_load_n(&g_udpdk.rx_refused, __ATOMIC_RELAXED); }
 
 /* ---- TX rings ----------------------------------------------------------------------------- */
 void h_tx_reset(void)
@@ -265,6 +266,9 @@ void h_sockets_reset(void)
     __atomic_store_n(&g_udpdk.rx_nobufs, 0, __ATOMIC_RELAXED);   /* per library session */
     __atomic_store_n(&g_udpdk.rx_dropped, 0, __ATOMIC_RELAXED);
     __atomic_store_n(&g_udpdk.rx_balanced, 0, __ATOMIC_RELAXED);
+    __atomic_store_n(&g_udpdk.rx_refused, 0, __ATOMIC_RELAXED);
+    g_udpdk.n_connected = 0;                   /* (the slots' peers went with the memset) */
+    g_udpdk.peer_version++;
     g_udpdk.version++;
 }
 
@@ -287,6 +291,7 @@ int udpdk_socket(int domain, int type, int protocol)
             sl->so_options = 0;
             sl->ip = 0;
             sl->udp_port = 0;
+            sl->connected = 0;
             sl->prev = sl->next = -1;
             g_udpdk.n_active++;
             ret = s;
@@ -374,6 +379,11 @@ int udpdk_close(int s)
     sl->tx.e = NULL;
     sl->tx.head = sl->tx.tail = 0;
     pthread_mutex_unlock(&g_udpdk.tx_lock);
+    if (sl->connected) {                       /* the peer goes with the socket */
+        sl->connected = 0;
+        g_udpdk.n_connected--;
+        g_udpdk.peer_version++;
+    }
     sl->bound = 0;
     sl->used = 0;
     sl->so_options = 0;
@@ -398,13 +408,35 @@ static int h_autobind_locked(int s)
     return h_bind_locked(s, (const struct sockaddr *)&a, sizeof(a));
 }
 
+/* The socket's peer as a sockaddr_in; returns whether it has one. g_udpdk.lock held. */
+static int h_peer_locked(int s, struct sockaddr_in *a)
+{
+    const struct h_slot *sl = &g_udpdk.slots[s];
+    memset(a, 0, sizeof(*a));
+    if (!sl->used || !sl->connected) return 0;
+    a->sin_family = AF_INET;
+    a->sin_port = sl->peer_port;
+    a->sin_addr.s_addr = sl->peer_ip;
+    return 1;
+}
+
 ssize_t udpdk_sendto(int s, const void *buf, size_t len, int flags,
                      const struct sockaddr *dest, socklen_t addrlen)
 {
     if (s < 0 || s >= UDPDK_MAX_SOCKETS) { errno = ENOTSOCK; return -1; }
     if (!g_udpdk.slots[s].used) { errno = EBADF; return -1; }
     if (flags != 0) { errno = EINVAL; return -1; }
-    if (!dest || addrlen == 0) { errno = EINVAL; return -1; }
+    struct sockaddr_in peer;
+    if (!dest) {
+        /* a connected socket's peer (udpdk_connect); unconnected: EINVAL as ever */
+        pthread_mutex_lock(&g_udpdk.lock);
+        const int conn = h_peer_locked(s, &peer);
+        pthread_mutex_unlock(&g_udpdk.lock);
+        if (!conn) { errno = EINVAL; return -1; }
+        dest = (const struct sockaddr *)&peer;
+        addrlen = sizeof(peer);
+    }
+    if (addrlen == 0) { errno = EINVAL; return -1; }
     if (len > H_UDP_MAX_PAYLOAD) { errno = EMSGSIZE; return -1; }
     if (len && !buf) { errno = EFAULT; return -1; }
     pthread_mutex_lock(&g_udpdk.lock);
@@ -514,6 +546,115 @@ ssize_t udpdk_recvfrom(int s, void *buf, size_t len, int flags,
     }
     atomic_fetch_sub_explicit(&r->busy, 1, memory_order_release);
     return (ssize_t)n;
+}
+
+/* ---- connected sockets -------------------------------------------------------------------- */
+int udpdk_connect(int s, const struct sockaddr *addr, socklen_t addrlen)
+{
+    if (s < 0 || s >= UDPDK_MAX_SOCKETS) { errno = ENOTSOCK; return -1; }
+    if (!g_udpdk.slots[s].used) { errno = EBADF; return -1; }
+    if (!addr || addrlen < sizeof(sa_family_t)) { errno = EINVAL; return -1; }
+    if (addr->sa_family != AF_INET && addr->sa_family != AF_UNSPEC) { errno = EAFNOSUPPORT; return -1; }
+    if (addr->sa_family == AF_INET && addrlen < sizeof(struct sockaddr_in)) { errno = EINVAL; return -1; }
+    int ret = -1;
+    pthread_mutex_lock(&g_udpdk.lock);
+    struct h_slot *sl = &g_udpdk.slots[s];
+    if (!sl->used) {
+        errno = EBADF;
+    } else if (addr->sa_family == AF_UNSPEC) {             /* dissolve the association */
+        if (sl->connected) {
+            sl->connected = 0;
+            g_udpdk.n_connected--;
+            g_udpdk.peer_version++;
+        }
+        ret = 0;
+    } else if (h_autobind_locked(s) == 0) {
+        const struct sockaddr_in *in = (const struct sockaddr_in *)addr;
+        if (!sl->connected) g_udpdk.n_connected++;
+        sl->connected = 1;
+        sl->peer_ip = in->sin_addr.s_addr;
+        sl->peer_port = in->sin_port;                      /* raw network-order value */
+        g_udpdk.peer_version++;                            /* the next poll uploads the table */
+        ret = 0;
+    }
+    pthread_mutex_unlock(&g_udpdk.lock);
+    return ret;
+}
+
+ssize_t udpdk_send(int s, const void *buf, size_t len, int flags)
+{
+    if (s < 0 || s >= UDPDK_MAX_SOCKETS) { errno = ENOTSOCK; return -1; }
+    if (!g_udpdk.slots[s].used) { errno = EBADF; return -1; }
+    struct sockaddr_in peer;
+    pthread_mutex_lock(&g_udpdk.lock);
+    const int conn = h_peer_locked(s, &peer);
+    pthread_mutex_unlock(&g_udpdk.lock);
+    if (!conn) { errno = ENOTCONN; return -1; }
+    return udpdk_sendto(s, buf, len, flags, (const struct sockaddr *)&peer, sizeof(peer));
+}
+
+ssize_t udpdk_recv(int s, void *buf, size_t len, int flags)
+{
+    return udpdk_recvfrom(s, buf, len, flags, NULL, NULL);
+}
+
+static int h_name_out(const struct sockaddr_in *a, struct sockaddr *addr, socklen_t *addrlen)
+{
+    const socklen_t n = sizeof(*a) <= *addrlen ? (socklen_t)sizeof(*a) : *addrlen;
+    memcpy(addr, a, n);
+    *addrlen = n;
+    return 0;
+}
+
+int udpdk_getpeername(int s, struct sockaddr *addr, socklen_t *addrlen)
+{
+    if (s < 0 || s >= UDPDK_MAX_SOCKETS) { errno = ENOTSOCK; return -1; }
+    if (!g_udpdk.slots[s].used) { errno = EBADF; return -1; }
+    if (!addr || !addrlen) { errno = EINVAL; return -1; }
+    struct sockaddr_in a;
+    pthread_mutex_lock(&g_udpdk.lock);
+    const int conn = h_peer_locked(s, &a);
+    pthread_mutex_unlock(&g_udpdk.lock);
+    if (!conn) { errno = ENOTCONN; return -1; }
+    return h_name_out(&a, addr, addrlen);
+}
+
+int udpdk_getsockname(int s, struct sockaddr *addr, socklen_t *addrlen)
+{
+    if (s < 0 || s >= UDPDK_MAX_SOCKETS) { errno = ENOTSOCK; return -1; }
+    if (!g_udpdk.slots[s].used) { errno = EBADF; return -1; }
+    if (!addr || !addrlen) { errno = EINVAL; return -1; }
+    struct sockaddr_in a;
+    memset(&a, 0, sizeof(a));
+    a.sin_family = AF_INET;
+    pthread_mutex_lock(&g_udpdk.lock);
+    const struct h_slot *sl = &g_udpdk.slots[s];
+    if (sl->used && sl->bound) {                           /* unbound: 0.0.0.0:0 */
+        a.sin_port = (uint16_t)sl->udp_port;
+        a.sin_addr.s_addr = sl->ip;
+    }
+    pthread_mutex_unlock(&g_udpdk.lock);
+    return h_name_out(&a, addr, addrlen);
+}
+
+int udpdk_peer_lanes(udpdk_peer_t *peers, uint32_t n)
+{
+    if (!peers && n) return -EINVAL;
+    int cnt = 0;
+    pthread_mutex_lock(&g_udpdk.lock);
+    for (uint32_t s = 0; s < UDPDK_MAX_SOCKETS; s++) {
+        const struct h_slot *sl = &g_udpdk.slots[s];
+        const int on = sl->used && sl->connected;
+        if (s < n) {
+            peers[s].ip = on ? sl->peer_ip : 0u;
+            peers[s].port = on ? sl->peer_port : 0u;
+            peers[s].on = (uint16_t)on;
+        }
+        cnt += on;
+    }
+    for (uint32_t s = UDPDK_MAX_SOCKETS; s < n; s++) memset(&peers[s], 0, sizeof(peers[s]));
+    pthread_mutex_unlock(&g_udpdk.lock);
+    return cnt;
 }
 
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots)

@@ -21,6 +21,7 @@
 #include "rx_plan.h"
 #include "rx_filter.h"
 #include "rx_balance.h"
+#include "rx_peer.h"
 #include "rss_host.h"
 
 using namespace udpdk;
@@ -108,8 +109,11 @@ struct Pipe {
     bool filtered = false;                    // this pipe's last call ran it
     BalanceWs bal;                            // sticky reuse-port balance
     bool balanced = false;                    // this pipe's last call ran it
+    FilterWs peer;                            // sticky peer filter (rx_peer.hip: the filter's workspace)
+    bool peered = false;                      // this pipe's last call ran it
     const udpdk_rx_stats_t *stats_of = nullptr;   // the stats block read_result filled last, and what
-    uint32_t n_dropped = 0, n_balanced = 0;       // each stage removed in that call (udpdk_gpu_rx_removed)
+    uint32_t n_dropped = 0, n_balanced = 0;       // each stage removed in that call (udpdk_gpu_rx_removed,
+    uint32_t n_refused = 0;                       // udpdk_gpu_rx_peer_removed)
     // host-resident batches (udpdk_gpu_rx_host[_async]): staging, lazily sized
     uint8_t *st_frames_d = nullptr; size_t st_frames_dcap = 0;
     uint8_t *st_frames_h = nullptr; size_t st_frames_hcap = 0;
@@ -174,6 +178,10 @@ struct udpdk_gpu_ctx {
                                               // udpdk_gpu_rss_config on this context)
     BalanceWs xbal;                           // explicit udpdk_gpu_rx_balance_select calls
     BalanceWs *bal_last = nullptr;            // the last balance run (udpdk_gpu_rx_balance_stats)
+    bool peer_on = false;                     // udpdk_gpu_rx_peer: the sticky peer filter
+    uint2 *peer_tab = nullptr;                // [max_lanes] its records (off past what was given)
+    FilterWs xpeer;                           // explicit udpdk_gpu_rx_peer_select calls
+    FilterWs *peer_last = nullptr;            // the last peer filter run (udpdk_gpu_rx_peer_stats)
     ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
 
     unsigned long long *dbg = nullptr;        // diagnostic stamp buffer (UDPDK_STAMPS builds)
@@ -467,8 +475,15 @@ int udpdk_gpu_ctx_destroy(udpdk_gpu_ctx *c)
         if (W->f.h_res) (void)hipHostFree(W->f.h_res);
         if (W->h_cnt) (void)hipHostFree(W->h_cnt);
     }
-    for (void *p : {(void *)c->bal_rp, (void *)c->bal_ktab})
+    for (void *p : {(void *)c->bal_rp, (void *)c->bal_ktab, (void *)c->peer_tab})
         if (p) (void)hipFree(p);
+    FilterWs *pw[MAX_PIPES + 1] = {&c->xpeer};
+    for (int i = 0; i < MAX_PIPES; ++i) pw[i + 1] = &c->pipes[i].peer;
+    for (FilterWs *W : pw) {
+        void *pd[] = {W->mask, W->row, W->base, W->pkt, W->off, W->res};
+        for (void *p : pd) if (p) (void)hipFree(p);
+        if (W->h_res) (void)hipHostFree(W->h_res);
+    }
     for (void *p : {(void *)c->rpl.row, (void *)c->rpl.base, (void *)c->rpl.res})
         if (p) (void)hipFree(p);
     if (c->rpl.h_res) (void)hipHostFree(c->rpl.h_res);
@@ -828,6 +843,58 @@ int balance_enqueue(udpdk_gpu_ctx *c, BalanceWs &B, hipStream_t st, const udpdk_
     return 0;
 }
 
+// The peer filter (rx_peer.hip) over one lane set on stream st: mark, then the filter's base and
+// write.
+int peer_enqueue(udpdk_gpu_ctx *c, FilterWs &W, hipStream_t st, const udpdk_rx_batch_t *bt,
+                 const udpdk_rx_lanes_t *in, const uint2 *peer, uint32_t *off_out, uint32_t *pkt_out,
+                 uint32_t out_cap)
+{
+    const uint32_t tiles = ceil_div(in->lane_cap, FLT_TILE);
+    int rc;
+    if ((rc = ensure_dev(c, (void **)&W.mask, &W.mask_cap, ((size_t)tiles * FLT_CHUNKS + 1) * 8)) ||
+        (rc = ensure_dev(c, (void **)&W.row, &W.row_cap, ((size_t)tiles * FLT_ROW + 1) * 4)) ||
+        (rc = ensure_dev(c, (void **)&W.base, &W.base_cap, ((size_t)tiles + 1) * 4)) ||
+        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(FilterResult))) ||
+        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(FilterResult))))
+        return rc;
+    PeerMarkArgs ma;
+    FilterArgs &fa = ma.f;
+    fa.meta = nullptr;
+    fa.lane_off = in->lane_off_dev;
+    fa.lane_pkt = in->lane_pkt_dev;
+    fa.lane_off_out = off_out;
+    fa.lane_pkt_out = pkt_out;
+    fa.mask = W.mask;
+    fa.row = W.row;
+    fa.base = W.base;
+    fa.res = W.res;
+    fa.n = in->n;
+    fa.lane_cap = in->lane_cap;
+    fa.n_lanes = in->n_lanes;
+    fa.flags = 0;
+    fa.out_cap = out_cap;
+    fa.n_tiles = tiles;
+    ma.peer = peer;
+    ma.frames = bt->frames_dev;
+    ma.offset = bt->offset_dev;
+    ma.length = bt->length_dev;
+    ma.frames_bytes = (uint32_t)bt->frames_bytes;
+    ma.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+    if (tiles) {
+        hipLaunchKernelGGL(rx_peer_mark, dim3(tiles), dim3(FLT_BLOCK), 0, st, ma);
+        HIPC(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(rx_filter_base, dim3(1), dim3(FLT_BASE_BLOCK), 0, st, fa);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(rx_filter_write, dim3(tiles + ceil_div(in->n_lanes + 1u, (uint32_t)FLT_BLOCK)),
+                       dim3(FLT_BLOCK), 0, st, fa);
+    HIPC(c, hipGetLastError());
+    W.stream = st;
+    W.out_cap = out_cap;
+    c->peer_last = &W;
+    return 0;
+}
+
 int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udpdk_rx_out_t *o);
 
 // One batch's RX on a pipe: the launch sequence that makes the lanes (whichever form it takes),
@@ -840,7 +907,8 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
     Pipe &P = c->pipes[pipe];
     P.filtered = false;
     P.balanced = false;
-    if ((!c->drop_flags && !c->bal_on) || bt->n == 0) return 0;   // (no frames: the lanes are empty)
+    P.peered = false;
+    if ((!c->drop_flags && !c->bal_on && !c->peer_on) || bt->n == 0) return 0;   // (no frames: the lanes are empty)
     const uint32_t S = c->n_lanes;
     const udpdk_rx_lanes_t in = {o->meta_dev, bt->n, o->lane_off_dev, o->lane_pkt_dev, o->lane_cap, S};
     const uint32_t tiles = ceil_div(o->lane_cap, FLT_TILE);
@@ -871,6 +939,21 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
                            o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
         HIPC(c, hipGetLastError());
         P.balanced = true;
+    }
+    if (c->peer_on) {
+        // after the other two, on what they left (all three are per-entry predicates that do not
+        // depend on what else the lanes hold, so they commute)
+        if (c->lane_mask != 0xFFFFFFFFu) return -EINVAL;       // compat mode: a lane is not a sockfd
+        FilterWs &W = P.peer;
+        if ((rc = ensure_dev(c, (void **)&W.pkt, &W.pkt_cap, ((size_t)o->lane_cap + 1) * 4)) ||
+            (rc = ensure_dev(c, (void **)&W.off, &W.off_cap, ((size_t)S + 1) * 4)))
+            return rc;
+        if ((rc = peer_enqueue(c, W, P.stream, bt, &in, c->peer_tab, W.off, W.pkt, o->lane_cap))) return rc;
+        hipLaunchKernelGGL(rx_filter_copy, dim3(tiles + ceil_div(S + 1u, (uint32_t)FLT_BLOCK)), dim3(FLT_BLOCK), 0,
+                           P.stream, (const uint32_t *)W.off, (const uint32_t *)W.pkt, (const FilterResult *)W.res,
+                           o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
+        HIPC(c, hipGetLastError());
+        P.peered = true;
     }
     return 0;
 }
@@ -1088,6 +1171,8 @@ int enqueue_result(udpdk_gpu_ctx *c, Pipe &P)
         HIPC(c, hipMemcpyAsync(P.flt.h_res, P.flt.res, sizeof(FilterResult), hipMemcpyDeviceToHost, P.stream));
     if (P.balanced)
         HIPC(c, hipMemcpyAsync(P.bal.f.h_res, P.bal.f.res, sizeof(FilterResult), hipMemcpyDeviceToHost, P.stream));
+    if (P.peered)
+        HIPC(c, hipMemcpyAsync(P.peer.h_res, P.peer.res, sizeof(FilterResult), hipMemcpyDeviceToHost, P.stream));
     return 0;
 }
 
@@ -1096,12 +1181,17 @@ int read_result(udpdk_gpu_ctx *c, Pipe &P, udpdk_rx_stats_t *st)
     for (int k = 0; k < UDPDK_N_COUNTERS; ++k) st->counters[k] = P.h_res->counters[k];
     // (sticky drop mode: the kept count; overflow stays the pre-filter total's)
     // (sticky balance mode: what it kept of that)
-    st->deliveries = P.balanced ? P.bal.f.h_res->kept : P.filtered ? P.flt.h_res->kept : P.h_res->total;
+    // (sticky peer filter: what it kept of that)
+    st->deliveries = P.peered     ? P.peer.h_res->kept
+                     : P.balanced ? P.bal.f.h_res->kept
+                     : P.filtered ? P.flt.h_res->kept
+                                  : P.h_res->total;
     for (Pipe &Q : c->pipes)
         if (Q.stats_of == st) Q.stats_of = nullptr;      // (a stats block reused across pipes)
     P.stats_of = st;
     P.n_dropped = P.filtered ? P.flt.h_res->removed : 0u;
     P.n_balanced = P.balanced ? P.bal.f.h_res->removed : 0u;
+    P.n_refused = P.peered ? P.peer.h_res->removed : 0u;
     st->overflow = P.h_res->total > P.last_lane_cap ? 1u : 0u;
     return st->overflow ? -ENOSPC : 0;
 }
@@ -1345,6 +1435,77 @@ int udpdk_gpu_rx_removed(udpdk_gpu_ctx *c, const udpdk_rx_stats_t *stats, uint32
         if (P.stats_of != stats) continue;
         *dropped = P.n_dropped;
         *balanced = P.n_balanced;
+        return 0;
+    }
+    return -ENOENT;
+}
+
+int udpdk_gpu_rx_peer_select(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_lanes_t *in,
+                             const udpdk_peer_t *peer_dev, uint32_t *lane_off_out_dev,
+                             uint32_t *lane_pkt_out_dev, uint32_t out_cap)
+{
+    if (!c || !bt || !in || !peer_dev || !lane_off_out_dev) return -EINVAL;
+    if (((uintptr_t)peer_dev & 7u) != 0) return -EINVAL;               // (the records load as 8-byte words)
+    if (in->n_lanes == 0 || in->n_lanes > UDPDK_GPU_MAX_LANES || !in->lane_off_dev) return -EINVAL;
+    if ((in->lane_cap && !in->lane_pkt_dev) || (out_cap && !lane_pkt_out_dev)) return -EINVAL;
+    if (bt->n != in->n || bt->frames_bytes >= (1ull << 32)) return -EINVAL;
+    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
+    if (!c->have_snapshot || c->lane_mask != 0xFFFFFFFFu) return -EINVAL;
+    const size_t offb = ((size_t)in->n_lanes + 1) * 4;
+    if (ranges_overlap(lane_off_out_dev, offb, in->lane_off_dev, offb) ||
+        ranges_overlap(lane_off_out_dev, offb, in->lane_pkt_dev, (size_t)in->lane_cap * 4) ||
+        ranges_overlap(lane_pkt_out_dev, (size_t)out_cap * 4, in->lane_off_dev, offb) ||
+        ranges_overlap(lane_pkt_out_dev, (size_t)out_cap * 4, in->lane_pkt_dev, (size_t)in->lane_cap * 4))
+        return -EINVAL;
+    HIPC(c, hipSetDevice(c->device));
+    if (c->depth > 1) { int r = join_pipes(c); if (r) return r; }
+    return peer_enqueue(c, c->xpeer, c->stream, bt, in, reinterpret_cast<const uint2 *>(peer_dev),
+                        lane_off_out_dev, lane_pkt_out_dev, out_cap);
+}
+
+int udpdk_gpu_rx_peer(udpdk_gpu_ctx *c, const udpdk_peer_t *peer_host, uint32_t n_lanes)
+{
+    if (!c || n_lanes > c->max_lanes) return -EINVAL;
+    HIPC(c, hipSetDevice(c->device));
+    { int rc = sync_all(c); if (rc) return rc; }             // (calls in flight read the records)
+    bool any = false;
+    for (uint32_t l = 0; peer_host && l < n_lanes; ++l) any = any || peer_host[l].on != 0;
+    if (!any) {
+        c->peer_on = false;
+        return 0;
+    }
+    if (!c->peer_tab) HIPC(c, hipMalloc((void **)&c->peer_tab, (size_t)c->max_lanes * sizeof(uint2)));
+    std::vector<uint2> tab(c->max_lanes, make_uint2(0u, 0u));
+    for (uint32_t l = 0; l < n_lanes; ++l)
+        if (peer_host[l].on) tab[l] = make_uint2(peer_host[l].ip, (uint32_t)peer_host[l].port | (1u << 16));
+    HIPC(c, hipMemcpy(c->peer_tab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    c->peer_on = true;
+    return 0;
+}
+
+int udpdk_gpu_rx_peer_stats(udpdk_gpu_ctx *c, udpdk_rx_peer_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    FilterWs *W = c->peer_last;
+    if (!W) return -ENOENT;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipMemcpyAsync(W->h_res, W->res, sizeof(FilterResult), hipMemcpyDeviceToHost, W->stream));
+    HIPC(c, hipStreamSynchronize(W->stream));
+    st->kept = W->h_res->kept;
+    st->removed = W->h_res->removed;
+    st->refused = (uint32_t)W->h_res->dropped[0];
+    st->bad_frame = (uint32_t)W->h_res->dropped[1];
+    st->bad_index = W->h_res->bad_index;
+    st->truncated = W->h_res->truncated;
+    return st->kept > W->out_cap ? -ENOSPC : 0;
+}
+
+int udpdk_gpu_rx_peer_removed(udpdk_gpu_ctx *c, const udpdk_rx_stats_t *stats, uint32_t *refused)
+{
+    if (!c || !stats || !refused) return -EINVAL;
+    for (const Pipe &P : c->pipes) {
+        if (P.stats_of != stats) continue;
+        *refused = P.n_refused;
         return 0;
     }
     return -ENOENT;
