@@ -10,15 +10,15 @@ LIB       := udpdk_amd/libudpdk_amd.so
 OBJDIR    := build/obj
 
 HIP_SRC   := udpdk_amd/csrc/rx_classify.hip udpdk_amd/csrc/rx_lanes.hip udpdk_amd/csrc/rx_gather.hip udpdk_amd/csrc/rx_reasm.hip \
-             udpdk_amd/csrc/rx_rss.hip udpdk_amd/csrc/tx_kernels.hip udpdk_amd/csrc/tx_reply.hip udpdk_amd/csrc/rx_filter.hip udpdk_amd/csrc/rx_balance.hip udpdk_amd/csrc/rx_peer.hip \
+             udpdk_amd/csrc/rx_rss.hip udpdk_amd/csrc/tx_kernels.hip udpdk_amd/csrc/tx_reply.hip udpdk_amd/csrc/rx_filter.hip udpdk_amd/csrc/rx_balance.hip udpdk_amd/csrc/rx_peer.hip udpdk_amd/csrc/icmp_reply.hip \
              udpdk_amd/csrc/udpdk_gpu.hip
 C_SRC     := $(wildcard udpdk_amd/csrc/host/*.c)
 HIP_OBJ   := $(patsubst udpdk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
 C_OBJ     := $(patsubst udpdk_amd/csrc/host/%.c,$(OBJDIR)/host/%.o,$(C_SRC))
 HDRS      := include/udpdk_gpu.h include/udpdk_api.h udpdk_amd/csrc/rx_common.h \
-             udpdk_amd/csrc/rx_plan.h udpdk_amd/csrc/rx_filter.h udpdk_amd/csrc/rx_balance.h udpdk_amd/csrc/rx_peer.h udpdk_amd/csrc/lane_find.h udpdk_amd/csrc/rss_toeplitz.h udpdk_amd/csrc/rss_host.h udpdk_amd/csrc/wave.h udpdk_amd/csrc/stamps.h $(wildcard udpdk_amd/csrc/host/*.h)
+             udpdk_amd/csrc/rx_plan.h udpdk_amd/csrc/rx_filter.h udpdk_amd/csrc/rx_balance.h udpdk_amd/csrc/rx_peer.h udpdk_amd/csrc/icmp_reply.h udpdk_amd/csrc/tx_ipv4.h udpdk_amd/csrc/lane_find.h udpdk_amd/csrc/rss_toeplitz.h udpdk_amd/csrc/rss_host.h udpdk_amd/csrc/wave.h udpdk_amd/csrc/stamps.h $(wildcard udpdk_amd/csrc/host/*.h)
 
-TOOLS     := tools/bin/bench_sock build/rx_plan_check build/rss_host_check build/echo_expand_check
+TOOLS     := tools/bin/bench_sock build/rx_plan_check build/rss_host_check build/echo_expand_check build/icmp_queue_check
 
 all: $(LIB) oracle $(TOOLS)
 
@@ -67,6 +67,17 @@ build/echo_expand_check: tools/echo_expand_check.c udpdk_amd/csrc/host/echo_expa
 	$(CC) -O1 -std=gnu11 -Wall -Wextra -Werror $(INC) $< -o $@
 echo-asan: build/echo_expand_check_asan
 build/echo_expand_check_asan: tools/echo_expand_check.c udpdk_amd/csrc/host/echo_expand.h
+	@mkdir -p build
+	$(CC) -O1 -g -std=gnu11 -Wall -Wextra -Werror -fsanitize=address,undefined -fno-sanitize-recover=all $(INC) $< -o $@
+
+# the host ICMP queue behind a main(): host code only, links no project library and runs on a machine
+# without a GPU (tests/test_icmp_ref.py); icmp-asan builds the same program with the address and
+# undefined-behaviour sanitizers (host only, never loaded into Python)
+build/icmp_queue_check: tools/icmp_queue_check.c udpdk_amd/csrc/host/icmp_queue.h
+	@mkdir -p build
+	$(CC) -O1 -std=gnu11 -Wall -Wextra -Werror $(INC) $< -o $@
+icmp-asan: build/icmp_queue_check_asan
+build/icmp_queue_check_asan: tools/icmp_queue_check.c udpdk_amd/csrc/host/icmp_queue.h
 	@mkdir -p build
 	$(CC) -O1 -g -std=gnu11 -Wall -Wextra -Werror -fsanitize=address,undefined -fno-sanitize-recover=all $(INC) $< -o $@
 
@@ -124,4 +135,4 @@ clean:
 	rm -rf build $(LIB) $(TOOLS)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean asm stamps pollprof variant rss-asan echo-asan FORCE
+.PHONY: all oracle clean asm stamps pollprof variant rss-asan echo-asan icmp-asan FORCE

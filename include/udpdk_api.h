@@ -127,7 +127,8 @@ int udpdk_poll_echo(const uint8_t *frames, uint64_t frames_bytes, const uint32_t
                     uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *out_len,
                     uint32_t max, uint32_t *n_out, udpdk_rx_stats_t *stats);
 
-/* Datagrams waiting in the TX rings. */
+/* Datagrams waiting in the TX rings, plus the ICMP frames queued for the next drain
+ * (udpdk_config_icmp). */
 uint64_t udpdk_tx_pending(void);
 
 /* Datagrams udpdk_tx_drain dropped because they needed more frames or bytes than a drain with
@@ -270,6 +271,39 @@ uint64_t udpdk_rx_refused(void);
 /* The records a poll uploads: peers[s] = socket s's peer (on = 1) or all zero, for s < n. Returns
  * how many sockets are connected (or -EINVAL). Host only, needs no GPU. */
 int udpdk_peer_lanes(udpdk_peer_t *peers, uint32_t n);
+
+/* ICMP answers (ini: [gpu] icmp = none | all | a comma list of echo, unreach). flags: UDPDK_ICMP_*
+ * bits (udpdk_gpu.h). 0 (default): as in the reference, an echo request ends as NOT_UDP and a
+ * datagram for a closed port is counted and forgotten. Otherwise udpdk_poll_rx, after a batch's RX
+ * and before reassembly, builds the answers on the GPU from the staged batch (udpdk_gpu_icmp_reply
+ * with the library's MACs, source address and MTU): an echo reply for every valid echo request to
+ * our address (the host answers `ping`), an ICMP port-unreachable for every valid datagram to our
+ * address that no socket is bound for (a client of a dead service gets ECONNREFUSED instead of a
+ * timeout). The frames are queued on the host, at most 4096 of them (later ones are dropped and
+ * counted), and udpdk_tx_drain emits them first, oldest first, in its usual format, the socket
+ * datagrams after them; a frame that does not fit the drain's max or out_cap stays queued.
+ * udpdk_tx_pending counts them. The one-piece and the chunked poll answer (a chunk on its pipe,
+ * replies queued in chunk order); fragments (the FRAG verdict) and datagrams reassembled from them
+ * are not answered, and neither is anything by udpdk_poll_echo. Sharded polls ([gpu] devices with
+ * two or more entries) do not answer: there a nonzero flags gives -1 with ENOTSUP, and udpdk_init
+ * fails on such an ini. With the loopback port the answers come back as ICMP types 0 and 3, which
+ * nothing answers. Returns the flags in force before the call; a negative argument only reads them;
+ * a bit outside UDPDK_ICMP_ALL: -1, EINVAL. */
+int udpdk_config_icmp(int flags);
+/* Port-unreachable errors answered per poll (ini: [gpu] icmp_burst = N; default 64, a policy default
+ * in the spirit of Linux's icmp_msgs_burst, not a measured value): the first N eligible datagrams
+ * of a poll in arrival order, counted across the chunks of a chunked poll; the rest are counted as
+ * limited. The limit is per poll, not per second: a poller that polls more often answers more. 0
+ * answers none, -1 means no limit; echo replies are not limited. Returns the value in force before
+ * the call; an argument below -1 only reads it. */
+int udpdk_config_icmp_burst(int n);
+/* Session sums over polls, like udpdk_rx_dropped: replies built (echo_replied, unreach_sent), echo
+ * requests refused for a bad length, checksum or an MTU overrun (echo_bad), errors beyond the burst
+ * (limited), and built frames the full queue dropped (queue_dropped). udpdk_host_reset zeroes them. */
+typedef struct {
+    uint64_t echo_replied, unreach_sent, echo_bad, limited, queue_dropped;
+} udpdk_icmp_counts_t;
+int udpdk_icmp_counts(udpdk_icmp_counts_t *counts);
 
 /* Socket slot state (exch_slot_info, udpdk_types.h:40-47) for the GPU TX slot table. */
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots);

@@ -51,7 +51,9 @@ extern "C" {
  *    (still 3: udpdk_gpu_rx_balance_select / udpdk_gpu_rx_balance / udpdk_gpu_rx_balance_stats /
  *    udpdk_gpu_rx_balance_rank / udpdk_gpu_rx_removed were added)
  *    (still 3: udpdk_gpu_rx_peer_select / udpdk_gpu_rx_peer / udpdk_gpu_rx_peer_stats /
- *    udpdk_gpu_rx_peer_removed were added) */
+ *    udpdk_gpu_rx_peer_removed were added)
+ *    (still 3: udpdk_gpu_icmp_reply / udpdk_gpu_icmp_stats / udpdk_gpu_icmp_geometry /
+ *    udpdk_gpu_pipe_icmp_reply / udpdk_gpu_pipe_icmp_stats were added) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -769,6 +771,100 @@ int udpdk_gpu_tx_reply_stats(udpdk_gpu_ctx *ctx, udpdk_tx_reply_stats_t *stats);
 /* Entries per workgroup of the plan kernels and the workgroup count for `count` entries (host
  * only, like udpdk_gpu_rx_geometry). */
 int udpdk_gpu_tx_reply_geometry(uint32_t count, uint32_t *entries_per_block, uint32_t *n_blocks);
+
+/* ---------------------------------------------------------------------------------------------
+ * ICMP on the device: echo replies and port-unreachable errors. The reference has no ICMP: an echo
+ * request ends as UDPDK_V_NOT_UDP and a datagram for a closed port as UDPDK_V_NO_BIND / NO_MATCH, and
+ * nothing looks at either again. This optional stage after udpdk_gpu_rx answers both from what is
+ * already in device memory (the verdict words, the staged frames): a host that runs this stack
+ * answers `ping`, and a client of a dead service gets ECONNREFUSED instead of waiting out its
+ * timeout (RFC 1122 §3.2.2.1, §4.1.3.1). Parity is against RFCs 792, 1071 and 1122. Off unless called.
+ *
+ * All addresses are raw. m = meta[i], tl = the big-endian u16 at frame bytes 16-17.
+ *
+ * Candidate by meta (no descriptor and no frame byte is read for any other frame, so a batch of UDP
+ * to bound ports costs the read of meta):
+ *   echo     flags & UDPDK_ICMP_ECHO, verdict NOT_UDP, UDPDK_META_IP_OK(m), !UDPDK_META_IHL_NE5(m)
+ *   unreach  flags & UDPDK_ICMP_UNREACH, verdict NO_BIND or NO_MATCH, IP_OK, !IHL_NE5,
+ *            UDPDK_META_UDP_CSUM(m) != UDPDK_UDP_CSUM_BAD and !UDPDK_META_LEN_BAD(m) (Linux drops a
+ *            datagram with a bad checksum before it reports the port)
+ * A candidate then passes the common gate:
+ *   - length[i] >= 42 and offset[i] + length[i] <= frames_bytes (64 bits), else it counts as
+ *     bad_frame and no frame byte is read (meta need not come from this batch);
+ *   - the destination address (bytes 30-33) == cfg->src_ip: unicast to us only, broadcast and
+ *     multicast are never answered (RFC 1122 §3.2.2);
+ *   - the first byte of the source address (byte 26) is not 0, not 127 and < 224.
+ *
+ * Echo request: an echo candidate past the gate with byte 23 == 1, byte 34 == 8, byte 35 == 0. It is
+ * answered iff 28 <= tl, 14 + tl <= length[i], mtu == 0 || tl <= mtu, and the one's-complement sum
+ * of bytes [34, 14 + tl) verifies (odd tail zero-padded; Ethernet padding past 14 + tl is neither
+ * summed nor copied); else it counts as echo_bad. The reply has 14 + tl bytes: Ethernet and IPv4
+ * headers as tx_build writes them for an unfragmented datagram (config MACs, 0x0800, 0x45, tos 0,
+ * id 0, fragment field 0, ttl 64, the same header checksum function) with total length tl,
+ * protocol 1, source cfg->src_ip, destination the request's source; then 00 00, the checksum, and
+ * request bytes [38, 14 + tl). The ICMP checksum is the full RFC 1071 value ~fold(sum) & 0xFFFF with
+ * no substitution: an all-zero reply carries FF FF, one summing to 0xFFFF carries 00 00.
+ *
+ * Port unreachable: of the unreach candidates past the gate (the eligible ones) the first err_limit
+ * in arrival order are answered, the rest count as limited (0xFFFFFFFF: no limit; 0: none). The
+ * reply has UDPDK_ICMP_UNREACH_BYTES: the headers as above with total length 56; 03 03, the
+ * checksum, 00 00 00 00; request bytes [14, 42) (the IPv4 header as received and the UDP header).
+ *
+ * Replies are in frame order, echo replies and errors interleaved. reply_off is the exclusive
+ * prefix (64 bits) of the lengths of the replies the limit leaves; reply r is written iff r <
+ * max_replies and its end <= out_cap, so the replies cut are a tail (no_room; no byte of theirs is
+ * written); reply_off[replies] is the end of the output. The limit applies before room: a cut error
+ * still used a slot of it. Fragments carry the FRAG verdict and are never answered.
+ *
+ * Asynchronous on the context stream; joins the pipes as udpdk_gpu_tx_build does. -EINVAL with
+ * nothing enqueued: a NULL pointer, flags 0 or with bits outside UDPDK_ICMP_ALL, frames_bytes or
+ * out_cap >= 2^32, an mtu udpdk_gpu_tx_build_mtu rejects, out->frames_dev not 16-byte aligned, an
+ * output that overlaps the frame buffer. n == 0 returns 0 with reply_off[0] = 0. The frames buffer
+ * keeps the tailroom contract of udpdk_gpu_rx. meta is read and never written. No snapshot is
+ * needed. The launches are not event-timed.
+ * ------------------------------------------------------------------------------------------- */
+#define UDPDK_ICMP_ECHO          1u   /* answer echo requests (type 8 -> type 0)            */
+#define UDPDK_ICMP_UNREACH       2u   /* answer UDP to a closed port with type 3 code 3     */
+#define UDPDK_ICMP_ALL           3u
+#define UDPDK_ICMP_UNREACH_BYTES 70u  /* 14 + 20 + 8 + 28                                    */
+
+typedef struct {
+    uint8_t  *frames_dev;     /* replies back to back, arrival order; 16-byte aligned base   */
+    uint64_t  out_cap;        /* < 2^32                                                      */
+    uint32_t *reply_off_dev;  /* [max_replies + 1]; reply r is [reply_off[r], reply_off[r+1]) */
+    uint32_t *origin_dev;     /* [max_replies] index of the frame reply r answers            */
+    uint32_t  max_replies;
+} udpdk_icmp_out_t;
+
+typedef struct {
+    uint64_t bytes_needed;    /* out_cap with which nothing is out of room                   */
+    uint32_t replies;         /* written: echo_replied + unreach_sent                        */
+    uint32_t echo_replied, unreach_sent;
+    uint32_t echo_bad;        /* echo requests past the gates with a bad length, checksum or tl > mtu */
+    uint32_t limited;         /* eligible errors beyond err_limit                            */
+    uint32_t no_room;         /* eligible replies cut by out_cap or max_replies (a tail)     */
+    uint32_t bad_frame;       /* candidate by meta, but length < 42 or out of range: not read */
+} udpdk_icmp_stats_t;
+
+int udpdk_gpu_icmp_reply(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg,
+                         const udpdk_rx_batch_t *batch, const uint32_t *meta_dev,
+                         uint32_t flags, uint32_t mtu, uint32_t err_limit,
+                         const udpdk_icmp_out_t *out);
+/* Of the last udpdk_gpu_icmp_reply on the context (-ENOENT when there was none). Synchronises.
+ * -ENOSPC when no_room > 0. */
+int udpdk_gpu_icmp_stats(udpdk_gpu_ctx *ctx, udpdk_icmp_stats_t *stats);
+/* Frames per workgroup of the scan and build kernels and the workgroup count for n frames (host
+ * only, like udpdk_gpu_tx_reply_geometry). */
+int udpdk_gpu_icmp_geometry(uint32_t n, uint32_t *frames_per_block, uint32_t *n_blocks);
+/* Poller internals: the same stage on pipe `pipe`'s stream (1 .. 3) with that pipe's workspace and
+ * no joins, like udpdk_gpu_pipe_gather_packed; the counts are copied to pinned memory on the same
+ * stream. udpdk_gpu_pipe_icmp_stats reads them without synchronising: they are those of the pipe's
+ * last stage once udpdk_gpu_pipe_wait has returned (-ENOENT: the pipe never ran one; -ENOSPC as above). */
+int udpdk_gpu_pipe_icmp_reply(udpdk_gpu_ctx *ctx, int pipe, const udpdk_tx_config_t *cfg,
+                              const udpdk_rx_batch_t *batch, const uint32_t *meta_dev,
+                              uint32_t flags, uint32_t mtu, uint32_t err_limit,
+                              const udpdk_icmp_out_t *out);
+int udpdk_gpu_pipe_icmp_stats(udpdk_gpu_ctx *ctx, int pipe, udpdk_icmp_stats_t *stats);
 
 /* ---------------------------------------------------------------------------------------------
  * Timing (for bench.py / the roofline): on every `enable`-th udpdk_gpu_rx call (0 = off, 1 =

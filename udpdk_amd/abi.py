@@ -187,6 +187,27 @@ class TxReplyStats(C.Structure):
                 ("frames", C.c_uint32)]
 
 
+ICMP_ECHO, ICMP_UNREACH, ICMP_ALL, ICMP_UNREACH_BYTES = 1, 2, 3, 70
+
+
+class IcmpOut(C.Structure):
+    """udpdk_icmp_out_t"""
+    _fields_ = [("frames_dev", C.c_void_p), ("out_cap", C.c_uint64), ("reply_off_dev", C.c_void_p),
+                ("origin_dev", C.c_void_p), ("max_replies", C.c_uint32)]
+
+
+class IcmpStats(C.Structure):
+    _fields_ = [("bytes_needed", C.c_uint64), ("replies", C.c_uint32), ("echo_replied", C.c_uint32),
+                ("unreach_sent", C.c_uint32), ("echo_bad", C.c_uint32), ("limited", C.c_uint32),
+                ("no_room", C.c_uint32), ("bad_frame", C.c_uint32)]
+
+
+class IcmpCounts(C.Structure):
+    """udpdk_icmp_counts_t (udpdk_api.h)"""
+    _fields_ = [("echo_replied", C.c_uint64), ("unreach_sent", C.c_uint64), ("echo_bad", C.c_uint64),
+                ("limited", C.c_uint64), ("queue_dropped", C.c_uint64)]
+
+
 # name -> (restype, argtypes); every symbol the headers declare
 _P = C.c_void_p
 _PROTOS = {
@@ -261,6 +282,13 @@ _PROTOS = {
                                      C.POINTER(TxReplyPlan)]),
     "udpdk_gpu_tx_reply_stats": (C.c_int, [_P, C.POINTER(TxReplyStats)]),
     "udpdk_gpu_tx_reply_geometry": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_icmp_reply": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.POINTER(IcmpOut)]),
+    "udpdk_gpu_icmp_stats": (C.c_int, [_P, C.POINTER(IcmpStats)]),
+    "udpdk_gpu_icmp_geometry": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_pipe_icmp_reply": (C.c_int, [_P, C.c_int, C.POINTER(TxConfig), C.POINTER(RxBatch), _P, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.POINTER(IcmpOut)]),
+    "udpdk_gpu_pipe_icmp_stats": (C.c_int, [_P, C.c_int, C.POINTER(IcmpStats)]),
     "udpdk_gpu_timing_enable": (C.c_int, [_P, C.c_int]),
     "udpdk_gpu_timing_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "udpdk_gpu_rx_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
@@ -302,6 +330,9 @@ _PROTOS = {
     "udpdk_config_reuseport": (C.c_int, [C.c_int]),
     "udpdk_rx_balanced": (C.c_uint64, []),
     "udpdk_reuseport_lanes": (C.c_int, [_P, C.c_uint32]),
+    "udpdk_config_icmp": (C.c_int, [C.c_int]),
+    "udpdk_config_icmp_burst": (C.c_int, [C.c_int]),
+    "udpdk_icmp_counts": (C.c_int, [C.POINTER(IcmpCounts)]),
     "udpdk_tx_pending": (C.c_uint64, []),
     "udpdk_tx_dropped": (C.c_uint64, []),
     "udpdk_rx_nobufs": (C.c_uint64, []),
@@ -846,6 +877,51 @@ def tx_reply_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, lane_off, lan
                      out_ptr=out_ptr)
 
 
+def icmp_geometry(n: int) -> tuple[int, int]:
+    """(frames per workgroup, workgroups) of the ICMP scan and build kernels for n frames."""
+    e = C.c_uint32()
+    k = C.c_uint32()
+    _check(lib().udpdk_gpu_icmp_geometry(n, C.byref(e), C.byref(k)), "udpdk_gpu_icmp_geometry")
+    return e.value, k.value
+
+
+def icmp_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, meta, *, flags: int = ICMP_ALL, mtu: int = 0,
+             err_limit: int = 0xFFFFFFFF, out_cap: int = 1 << 20, max_replies=None, n=None, pipe: int = 0,
+             pad: int = 8, guard: int = 4096):
+    """udpdk_gpu_icmp_reply (pipe 0) or udpdk_gpu_pipe_icmp_reply + udpdk_gpu_pipe_wait over host verdict
+    words. Returns a dict: rc of the call, rc and struct of the stats call, reply_off and origin as
+    downloaded (`pad` elements longer than the call may write, pre-filled with 0xA5 bytes) and out:
+    out_cap + guard bytes pre-filled with 0xEE."""
+    meta = np.ascontiguousarray(meta, np.uint32)
+    n = b.n if n is None else n
+    max_replies = n if max_replies is None else max_replies
+    bufs = [ctx.upload(meta), ctx.upload(np.full(4 * (max_replies + 1 + pad), 0xA5, np.uint8)),
+            ctx.upload(np.full(4 * (max_replies + pad), 0xA5, np.uint8)),
+            ctx.upload(np.full(out_cap + guard, 0xEE, np.uint8))]
+    try:
+        bt = RxBatch(b.frames.ptr, b.frames_bytes, b.offset.ptr, b.length.ptr,
+                     b.ptype.ptr if b.ptype is not None else None, n)
+        o = IcmpOut(bufs[3].ptr, out_cap, bufs[1].ptr, bufs[2].ptr, max_replies)
+        st = IcmpStats()
+        if pipe:
+            rc = lib().udpdk_gpu_pipe_icmp_reply(ctx.handle, pipe, C.byref(cfg), C.byref(bt), C.c_void_p(bufs[0].ptr),
+                                                 flags, mtu, err_limit, C.byref(o))
+            _check(lib().udpdk_gpu_pipe_wait(ctx.handle, pipe), "udpdk_gpu_pipe_wait")
+            src = lib().udpdk_gpu_pipe_icmp_stats(ctx.handle, pipe, C.byref(st))
+        else:
+            rc = lib().udpdk_gpu_icmp_reply(ctx.handle, C.byref(cfg), C.byref(bt), C.c_void_p(bufs[0].ptr), flags,
+                                            mtu, err_limit, C.byref(o))
+            src = lib().udpdk_gpu_icmp_stats(ctx.handle, C.byref(st))
+        ctx.sync()
+        return {"rc": rc, "stats_rc": src, "stats": st,
+                "reply_off": ctx.download(bufs[1], np.uint32, max_replies + 1 + pad),
+                "origin": ctx.download(bufs[2], np.uint32, max_replies + pad),
+                "out": ctx.download(bufs[3], np.uint8, out_cap + guard)}
+    finally:
+        for x in bufs:
+            x.free()
+
+
 @dataclass
 class DevRef:
     """A device pointer the context owns (no free)."""
@@ -1067,6 +1143,17 @@ class HostApi:
                                     _ptr(off), _ptr(ln), max_frames, C.byref(n), C.byref(st))
         err = self.errno() if rc != 0 else 0
         return rc, err, [bytes(out[off[i]:off[i] + ln[i]]) for i in range(n.value if rc == 0 else 0)], st, n.value
+
+    def config_icmp(self, flags: int) -> int:
+        return lib().udpdk_config_icmp(int(flags))
+
+    def config_icmp_burst(self, n: int) -> int:
+        return lib().udpdk_config_icmp_burst(int(n))
+
+    def icmp_counts(self) -> IcmpCounts:
+        c = IcmpCounts()
+        _check(lib().udpdk_icmp_counts(C.byref(c)), "udpdk_icmp_counts")
+        return c
 
     def tx_pending(self) -> int:
         return int(self.L.udpdk_tx_pending())

@@ -17,6 +17,7 @@
 #include <sys/types.h>
 
 #include "udpdk_api.h"
+#include "icmp_queue.h"
 
 /* Linux values the reference relies on (udpdk_syscall.c:102-105, :167, :174). */
 #define H_SO_REUSEADDR 2
@@ -246,6 +247,16 @@ struct h_state {
      * copy, the device lanes + reply plan, the built replies, the pinned readback of the plan */
     void     *ec_h, *ec_in_d, *ec_ws_d, *ec_out_d, *ec_rb_h;
     uint64_t  ec_h_cap, ec_in_d_cap, ec_ws_d_cap, ec_out_d_cap, ec_rb_h_cap;
+    /* ICMP answers (rx_icmp.c): [gpu] icmp / udpdk_config_icmp flags (0: a poll enqueues what it always
+     * did), [gpu] icmp_burst (errors answered per poll, -1: no limit), the queue udpdk_tx_drain empties
+     * first and the session's counts (both under tx_lock); work buffers, grow-only: the device
+     * output, reply_off + origin, the pinned readback */
+    uint32_t  icmp_flags;
+    int32_t   icmp_burst;
+    struct h_icmpq icmpq;
+    udpdk_icmp_counts_t icmp_counts;
+    void     *ic_out_d, *ic_idx_d, *ic_h;
+    uint64_t  ic_out_d_cap, ic_idx_d_cap, ic_h_cap;
     /* poller thread (udpdk_port_attach) */
     pthread_t poller;
     atomic_int poller_run;
@@ -306,5 +317,13 @@ void h_tx_buffers_free(void);
 
 /* rx_echo.c */
 void h_echo_buffers_free(void);
+
+/* rx_icmp.c */
+#define H_ICMP_BURST_DEFAULT 64   /* a policy default in the spirit of Linux's icmp_msgs_burst, not measured */
+void h_icmp_reset(void);                  /* under tx_lock */
+void h_icmp_buffers_free(void);
+uint32_t h_icmp_budget(void);
+int  h_icmp_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const uint32_t *meta_dev,
+                  uint32_t *budget);
 
 #endif

@@ -42,6 +42,8 @@ static void h_config_defaults(void)
     g_udpdk.tx_udp_cksum = 0;          /* UDP checksum 0 on TX, udpdk_syscall.c:343 */
     g_udpdk.rx_drop = 0;               /* every delivery reaches its socket, as in the reference */
     g_udpdk.reuseport = UDPDK_REUSEPORT_FANOUT;   /* every reuse socket gets a clone, as in the reference */
+    g_udpdk.icmp_flags = 0;            /* no ICMP answers, as in the reference */
+    g_udpdk.icmp_burst = H_ICMP_BURST_DEFAULT;
     g_udpdk.arena_bytes_max = 4ull << 30;
     g_udpdk.arena_count_max = 1024;
     g_udpdk.port_spec[0] = g_udpdk.port_peer[0] = 0;
@@ -69,6 +71,7 @@ void udpdk_host_reset(void)
     pthread_mutex_lock(&g_udpdk.tx_lock);
     h_btable_reset();
     h_sockets_reset();
+    h_icmp_reset();
     pthread_mutex_unlock(&g_udpdk.tx_lock);
     atomic_store(&g_udpdk.interrupted, 0);
     g_udpdk.snap_version = UINT64_MAX;
@@ -76,6 +79,8 @@ void udpdk_host_reset(void)
     g_udpdk.tx_udp_cksum = 0;
     g_udpdk.rx_drop = 0;
     g_udpdk.reuseport = UDPDK_REUSEPORT_FANOUT;
+    g_udpdk.icmp_flags = 0;
+    g_udpdk.icmp_burst = H_ICMP_BURST_DEFAULT;
     pthread_mutex_unlock(&g_udpdk.lock);
 }
 
@@ -207,6 +212,26 @@ static int h_parse_rx_drop(const char *v)
     }
 }
 
+/* "[gpu] icmp": none | all | a comma list of echo, unreach -> UDPDK_ICMP_* flags, or -1. */
+static int h_parse_icmp(const char *v)
+{
+    if (!strcmp(v, "none")) return 0;
+    if (!strcmp(v, "all")) return (int)UDPDK_ICMP_ALL;
+    uint32_t fl = 0;
+    const char *p = v;
+    for (;;) {
+        while (*p == ' ' || *p == '\t') p++;
+        const size_t l = strcspn(p, ", \t");
+        if (l == 4 && !strncmp(p, "echo", 4)) fl |= UDPDK_ICMP_ECHO;
+        else if (l == 7 && !strncmp(p, "unreach", 7)) fl |= UDPDK_ICMP_UNREACH;
+        else return -1;
+        p += l;
+        while (*p == ' ' || *p == '\t') p++;
+        if (!*p) return (int)fl;
+        if (*p++ != ',') return -1;
+    }
+}
+
 /* Minimal INI reader for the keys the reference understands plus a [gpu] section. */
 static int h_load_ini(const char *path)
 {
@@ -287,6 +312,18 @@ static int h_load_ini(const char *path)
             if (!strcmp(v, "fanout")) udpdk_config_reuseport(UDPDK_REUSEPORT_FANOUT);
             else if (!strcmp(v, "balance")) udpdk_config_reuseport(UDPDK_REUSEPORT_BALANCE);
             else { rc = -1; break; }
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "icmp")) {
+            /* none (default) | all | a comma list of echo, unreach: what a poll answers on the GPU
+             * (UDPDK_ICMP_*); checked against [gpu] devices once the file is read */
+            const int fl = h_parse_icmp(v);
+            if (fl < 0) { rc = -1; break; }
+            g_udpdk.icmp_flags = (uint32_t)fl;
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "icmp_burst")) {
+            /* port-unreachable errors answered per poll (not per second); 0: none, -1: no limit */
+            char *e;
+            const long b = strtol(v, &e, 0);
+            if (e == v || *e || b < -1 || b > INT32_MAX) { rc = -1; break; }
+            g_udpdk.icmp_burst = (int32_t)b;
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port")) {
             snprintf(g_udpdk.port_spec, sizeof(g_udpdk.port_spec), "%s", v);
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port_peer")) {
@@ -299,6 +336,8 @@ static int h_load_ini(const char *path)
         /* [dpdk] lcores / n_mem_channels configure EAL, which does not exist here */
     }
     fclose(f);
+    /* sharded polls do not answer (udpdk_config_icmp: ENOTSUP) */
+    if (!rc && g_udpdk.icmp_flags && g_udpdk.n_shards > 1) rc = -1;
     return rc;
 }
 
@@ -403,6 +442,7 @@ void udpdk_cleanup(void)
     h_rx_buffers_free();
     h_tx_buffers_free();
     h_echo_buffers_free();
+    h_icmp_buffers_free();
     h_arenas_free_all();
     g_udpdk.frag_ready = 0;
     h_shards_destroy();

@@ -1196,6 +1196,7 @@ static int h_poll_chunked(const uint8_t *frames, uint64_t frames_bytes, const ui
     struct h_adm A;
     udpdk_rx_stats_t tot;
     memset(&tot, 0, sizeof(tot));
+    uint32_t icmp_budget = h_icmp_budget();      /* errors this poll may answer, over all its chunks */
 #define CK_ISSUE(k) udpdk_gpu_pipe_rx_host(g, h_pipe_of(k), frames + ck[k].lo, ck[k].bytes, offset + ck[k].f0,     \
                                            (uint32_t)ck[k].lo, length + ck[k].f0, ptype ? ptype + ck[k].f0 : NULL, \
                                            ck[k].n, g_udpdk.pc_meta + ck[k].f0, g_udpdk.pc_loff + (uint64_t)L1 * (k), \
@@ -1233,6 +1234,8 @@ static int h_poll_chunked(const uint8_t *frames, uint64_t frames_bytes, const ui
         if ((rc = udpdk_gpu_pipe_batch(g, h_pipe_of(k), &staged, &meta_dev))) { err = -rc; break; }
         uint32_t nd = 0;
         const uint64_t nfrag = C->st.counters[UDPDK_V_FRAG];
+        /* [gpu] icmp: the chunk's answers, on its pipe, before reassembly touches the frames */
+        if (h_icmp_stage(g, h_pipe_of(k), &staged, meta_dev, &icmp_budget)) { err = errno; break; }
         if (h_frag_pass(&staged, meta_dev, nfrag, lanes, maxfan, 1, &rb, &nd)) { err = errno; break; }
         CPROF_T(t1); CPROF_ADD(4, t0, t1); t0 = t1;
         const uint32_t *floff = nd ? g_udpdk.fr_loff : NULL;
@@ -1368,6 +1371,10 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
             goto out;
         for (uint32_t d = 0; d < nd; d++) g_udpdk.fr_org[d] = g_udpdk.fb_idx[g_udpdk.fr_org[d]];
     } else if (!sharded) {
+        /* [gpu] icmp: echo replies and port-unreachable errors for the staged batch, queued for
+         * udpdk_tx_drain, before reassembly touches the frames (nothing is enqueued with flags 0) */
+        uint32_t icmp_budget = h_icmp_budget();
+        if (h_icmp_stage(g, 0, &staged, meta_dev, &icmp_budget)) goto out;
         const int inplace = nfrag && h_desc_disjoint(offset, length, n, frames_bytes);
         if (h_frag_pass(&staged, meta_dev, nfrag, lanes, maxfan, inplace, &rb, &nd)) goto out;
     }

@@ -236,7 +236,7 @@ void h_tx_reset(void)
 uint64_t udpdk_tx_pending(void)
 {
     pthread_mutex_lock(&g_udpdk.tx_lock);
-    const uint64_t q = g_udpdk.tx_queued;
+    const uint64_t q = g_udpdk.tx_queued + g_udpdk.icmpq.count;   /* (the poller gates its drain on this) */
     pthread_mutex_unlock(&g_udpdk.tx_lock);
     return q;
 }

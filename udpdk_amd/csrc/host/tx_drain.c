@@ -9,6 +9,10 @@
  * (Ethernet/IPv4/UDP headers from the slot table of the uploaded bind snapshot, rte_ipv4_cksum,
  * payload copy, fragmentation at the MTU, the UDP checksum with [gpu] tx_udp_cksum = 1) and one
  * D2H returns them.
+ *
+ * ICMP frames a poll built (rx_icmp.c) leave first, oldest first, copied from their host queue; the
+ * socket datagrams follow in what room is left. A queued ICMP frame that does not fit the caller's
+ * limits stays queued, and the datagrams wait behind it for the next drain.
  */
 #include <errno.h>
 #include <stdlib.h>
@@ -66,6 +70,14 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
     pthread_mutex_lock(&g_udpdk.tx_lock);
     pthread_mutex_unlock(&g_udpdk.lock);
     int ret = -1, rc;
+    /* 0. the queued ICMP frames */
+    uint32_t k0 = 0;
+    uint64_t b0 = 0;
+    h_icmpq_drain(&g_udpdk.icmpq, out, out_cap, out_off, out_len, max, &k0, &b0);
+    *n_out = k0;
+    if (g_udpdk.icmpq.count) { ret = 0; goto out; }
+    const uint32_t max_s = max - k0;
+    const uint64_t cap_s = out_cap - b0;
     /* 1. selection in the poller's order */
     uint32_t nsel = 0, nframes = 0, burst = 0;
     uint64_t bytes = 0, pay = 0;
@@ -81,7 +93,7 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
                 const struct h_txd *t = &q->e[(q->head + taken[s]) % UDPDK_RX_RING_SIZE];
                 uint32_t nf = 1;
                 const uint64_t span = udpdk_gpu_tx_span(t->len, mtu, &nf);
-                if (nframes + nf > max || bytes + span > out_cap) {
+                if (nframes + nf > max_s || bytes + span > cap_s) {
                     if (nframes == 0 && taken[s] == 0 && (nf > max || span > out_cap)) {
                         /* larger than any drain with these limits can carry: it would block
                          * the ring's head forever. Dropped and counted (udpdk_tx_dropped), as
@@ -160,17 +172,17 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
                           (const uint16_t *)(d + o_port), nsel};
     udpdk_tx_out_t o = {g_udpdk.tx_fr_d, bytes + 64, (const uint32_t *)(d + o_foff)};
     if ((rc = udpdk_gpu_h2d(g, d, h, tot)) || (rc = udpdk_gpu_tx_build_flags(g, &cfg, &b, &o, mtu, txf)) ||
-        (rc = udpdk_gpu_d2h(g, out, g_udpdk.tx_fr_d, bytes)) || (rc = udpdk_gpu_sync(g))) {
+        (rc = udpdk_gpu_d2h(g, out + b0, g_udpdk.tx_fr_d, bytes)) || (rc = udpdk_gpu_sync(g))) {
         errno = -rc;
         goto out;
     }
     /* 4. frame table, dequeue, payload store compaction */
-    uint32_t k = 0;
+    uint32_t k = k0;
     for (uint32_t i = 0; i < nsel; i++) {
         const uint32_t nf = g_udpdk.tx_sel[i].nf;
         const uint64_t span = udpdk_gpu_tx_span(len[i], mtu, NULL);
         for (uint32_t f = 0; f < nf; f++) {
-            out_off[k] = foff[i] + f * (mtu + 14u);
+            out_off[k] = (uint32_t)b0 + foff[i] + f * (mtu + 14u);
             out_len[k] = (uint16_t)(f + 1 < nf ? mtu + 14u : span - (uint64_t)(nf - 1) * (mtu + 14u));
             k++;
         }

@@ -28,6 +28,7 @@
 #include "udpdk_gpu.h"
 #include "rx_common.h"
 #include "wave.h"
+#include "tx_ipv4.h"
 
 namespace udpdk {
 
@@ -60,23 +61,7 @@ __device__ __forceinline__ uint32_t sel4(uint32_t d, uint32_t a0, uint32_t a1, u
     return d == 0 ? a0 : (d == 1 ? a1 : (d == 2 ? a2 : a3));
 }
 
-// Sum of the 20-byte IPv4 header built below (checksum field zero) as LE 16-bit words:
-// version/IHL 0x45, tos 0, total length tl, id 0, fragment field ff (host order), ttl 64,
-// proto 17, src, dst (raw).
-__device__ __forceinline__ uint32_t ipv4_raw(uint32_t tl, uint32_t ff, uint32_t src, uint32_t dst)
-{
-    uint32_t s = 0x0045u + bswap16(tl) + bswap16(ff) + 0x1140u + (src & 0xFFFFu) + (src >> 16) +
-                 (dst & 0xFFFFu) + (dst >> 16);
-    s = (s >> 16) + (s & 0xFFFFu);
-    s = (s >> 16) + (s & 0xFFFFu);
-    return s & 0xFFFFu;
-}
-
-// rte_ipv4_cksum of DPDK 20.05: raw == 0xffff is returned unchanged.
-__device__ __forceinline__ uint32_t ipv4_cksum(uint32_t raw) { return raw == 0xFFFFu ? raw : (~raw & 0xFFFFu); }
-
-// The checksum a NIC computes for PKT_TX_IP_CKSUM (fragments, rte_ipv4_fragment_packet leaves 0).
-__device__ __forceinline__ uint32_t ipv4_cksum_nic(uint32_t raw) { return ~raw & 0xFFFFu; }
+// (ipv4_raw, ipv4_cksum, ipv4_cksum_nic: tx_ipv4.h, shared with icmp_build)
 
 // The RFC 768 terms that are not payload, as LE 16-bit words like ipv4_raw: the pseudo-header
 // (src, dst, zero, 17, UDP length) and the UDP header (raw ports, length, checksum field 0).

@@ -22,6 +22,7 @@
 #include "rx_filter.h"
 #include "rx_balance.h"
 #include "rx_peer.h"
+#include "icmp_reply.h"
 #include "rss_host.h"
 
 using namespace udpdk;
@@ -82,6 +83,17 @@ struct ReplyWs {
     bool ran = false;                                 // a plan was enqueued (udpdk_gpu_tx_reply_stats)
 };
 
+// Workspace of the ICMP reply stage (icmp_reply.hip), lazily sized by the context's max_frames: one
+// for the context stream (udpdk_gpu_icmp_reply) and one per pipe (udpdk_gpu_pipe_icmp_reply).
+struct IcmpWs {
+    IcmpEntry *cand = nullptr; size_t cand_cap = 0;
+    uint32_t *row = nullptr; size_t row_cap = 0;       // the rows, then ubase and rbase
+    unsigned long long *bbase = nullptr; size_t bbase_cap = 0;
+    IcmpResult *res = nullptr; size_t res_cap = 0;
+    IcmpResult *h_res = nullptr; size_t h_res_cap = 0;     // pinned mirror
+    bool ran = false;                                 // a stage was enqueued (udpdk_gpu_icmp_stats)
+};
+
 // One RX pipe = a stream and the per-call workspace. With pipelining depth d > 1, consecutive
 // udpdk_gpu_rx calls rotate over d pipes, so one batch's prologue, tail and compaction overlap
 // the other batches' streaming phases (the calls are independent: distinct batches and output
@@ -123,6 +135,7 @@ struct Pipe {
     udpdk_rx_stats_t *host_stats = nullptr;   // outstanding async host call: where its stats go
     udpdk_rx_batch_t staged{};                // device view of the last host batch staged here
     const uint32_t *staged_meta = nullptr;    // and its verdict words
+    IcmpWs icmp;                              // udpdk_gpu_pipe_icmp_reply on this pipe's stream
 };
 constexpr int MAX_PIPES = 4;
 constexpr size_t FUSE_BYTES = 128u * UDPDK_FUSE_LINES;   // one 128-B line per fan-in / repair word
@@ -183,6 +196,7 @@ struct udpdk_gpu_ctx {
     FilterWs xpeer;                           // explicit udpdk_gpu_rx_peer_select calls
     FilterWs *peer_last = nullptr;            // the last peer filter run (udpdk_gpu_rx_peer_stats)
     ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
+    IcmpWs icmp;                              // udpdk_gpu_icmp_reply (the context stream)
 
     unsigned long long *dbg = nullptr;        // diagnostic stamp buffer (UDPDK_STAMPS builds)
     Reasm *reasm = nullptr;                   // udpdk_gpu_frag_table_create
@@ -487,6 +501,13 @@ int udpdk_gpu_ctx_destroy(udpdk_gpu_ctx *c)
     for (void *p : {(void *)c->rpl.row, (void *)c->rpl.base, (void *)c->rpl.res})
         if (p) (void)hipFree(p);
     if (c->rpl.h_res) (void)hipHostFree(c->rpl.h_res);
+    IcmpWs *iw[MAX_PIPES + 1] = {&c->icmp};
+    for (int i = 0; i < MAX_PIPES; ++i) iw[i + 1] = &c->pipes[i].icmp;
+    for (IcmpWs *W : iw) {
+        void *pd[] = {W->cand, W->row, W->bbase, W->res};
+        for (void *p : pd) if (p) (void)hipFree(p);
+        if (W->h_res) (void)hipHostFree(W->h_res);
+    }
     for (Pipe &P : c->pipes) {
         void *ph[] = {P.st_frames_h, P.st_desc_h};
         for (void *p : ph) if (p) (void)hipHostFree(p);
@@ -2039,6 +2060,155 @@ int udpdk_gpu_tx_reply_stats(udpdk_gpu_ctx *c, udpdk_tx_reply_stats_t *st)
     st->no_room = W.h_res->no_room;
     st->frames = W.h_res->frames;
     return st->no_room ? -ENOSPC : 0;
+}
+
+namespace {
+
+// Argument checks of udpdk_gpu_icmp_reply and its pipe form: nothing is enqueued unless all pass.
+int icmp_check(const udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
+               const uint32_t *meta_dev, uint32_t flags, uint32_t mtu, const udpdk_icmp_out_t *o)
+{
+    if (!c || !cfg || !bt || !meta_dev || !o) return -EINVAL;
+    if (!flags || (flags & ~UDPDK_ICMP_ALL)) return -EINVAL;
+    if (mtu && (mtu < 68u || mtu > 65535u || (mtu - 20u) % 8u)) return -EINVAL;
+    if (bt->frames_bytes >= (1ull << 32) || o->out_cap >= (1ull << 32)) return -EINVAL;
+    if (!o->frames_dev || !o->reply_off_dev || !o->origin_dev) return -EINVAL;
+    if ((uintptr_t)o->frames_dev & 15u) return -EINVAL;
+    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
+    if (bt->frames_dev) {
+        // the frame buffer with its tailroom against [frames_dev, frames_dev + out_cap)
+        const uintptr_t f0 = (uintptr_t)bt->frames_dev, f1 = f0 + bt->frames_bytes + UDPDK_GPU_FRAMES_TAILROOM;
+        const uintptr_t o0 = (uintptr_t)o->frames_dev, o1 = o0 + o->out_cap;
+        if (o0 < f1 && f0 < o1) return -EINVAL;
+    }
+    return 0;
+}
+
+// The stage (icmp_reply.hip) on stream st with workspace W: scan, base, build.
+int icmp_enqueue(udpdk_gpu_ctx *c, IcmpWs &W, hipStream_t st, const udpdk_tx_config_t *cfg,
+                 const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, uint32_t flags, uint32_t mtu,
+                 uint32_t err_limit, const udpdk_icmp_out_t *o)
+{
+    const uint32_t nb = ceil_div(bt->n, ICMP_TILE);
+    const size_t rows = std::max<size_t>(ceil_div(std::max(bt->n, c->max_frames), ICMP_TILE), 1);
+    int rc;
+    if ((rc = ensure_dev(c, (void **)&W.cand, &W.cand_cap, rows * ICMP_TILE * sizeof(IcmpEntry))) ||
+        (rc = ensure_dev(c, (void **)&W.row, &W.row_cap, rows * (ICMP_ROW + 2) * 4)) ||
+        (rc = ensure_dev(c, (void **)&W.bbase, &W.bbase_cap, rows * 8)) ||
+        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(IcmpResult))) ||
+        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(IcmpResult))))
+        return rc;
+    if (!bt->n) {
+        HIPC(c, hipMemsetAsync(o->reply_off_dev, 0, 4, st));
+        HIPC(c, hipMemsetAsync(W.res, 0, sizeof(IcmpResult), st));
+        W.ran = true;
+        return 0;
+    }
+    IcmpArgs ia;
+    ia.frames = bt->frames_dev;
+    ia.offset = bt->offset_dev;
+    ia.length = bt->length_dev;
+    ia.meta = meta_dev;
+    ia.out = o->frames_dev;
+    ia.reply_off = o->reply_off_dev;
+    ia.origin = o->origin_dev;
+    ia.cand = W.cand;
+    ia.row = W.row;
+    ia.ubase = W.row + (size_t)ICMP_ROW * nb;
+    ia.rbase = ia.ubase + nb;
+    ia.bbase = W.bbase;
+    ia.res = W.res;
+    ia.n = bt->n;
+    ia.n_blocks = nb;
+    ia.frames_bytes = (uint32_t)bt->frames_bytes;
+    ia.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+    ia.flags = flags;
+    ia.mtu = mtu;
+    ia.err_limit = err_limit;
+    ia.out_cap = (uint32_t)o->out_cap;
+    ia.max_replies = o->max_replies;
+    ia.src_ip = cfg->src_ip;
+    uint8_t mac[12];
+    memcpy(mac, cfg->dst_mac, 6);   // Ethernet d_addr first, as tx_build
+    memcpy(mac + 6, cfg->src_mac, 6);
+    memcpy(ia.mac_lo, mac, 12);
+    hipLaunchKernelGGL(icmp_scan, dim3(nb), dim3(ICMP_BLOCK), 0, st, ia);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(icmp_base, dim3(1), dim3(ICMP_BASE_BLOCK), 0, st, ia);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(icmp_build, dim3(nb), dim3(ICMP_BLOCK), 0, st, ia);
+    HIPC(c, hipGetLastError());
+    W.ran = true;
+    return 0;
+}
+
+int icmp_stats_out(const IcmpResult *r, udpdk_icmp_stats_t *st)
+{
+    st->bytes_needed = r->bytes_needed;
+    st->echo_replied = r->echo_replied;
+    st->unreach_sent = r->unreach_sent;
+    st->replies = r->echo_replied + r->unreach_sent;
+    st->echo_bad = r->echo_bad;
+    st->limited = r->limited;
+    st->no_room = r->no_room;
+    st->bad_frame = r->bad_frame;
+    return st->no_room ? -ENOSPC : 0;
+}
+
+} // namespace
+
+int udpdk_gpu_icmp_geometry(uint32_t n, uint32_t *frames_per_block, uint32_t *n_blocks)
+{
+    if (!frames_per_block || !n_blocks) return -EINVAL;
+    *frames_per_block = ICMP_TILE;
+    *n_blocks = std::max<uint32_t>(1u, ceil_div(n, ICMP_TILE));
+    return 0;
+}
+
+int udpdk_gpu_icmp_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
+                         const uint32_t *meta_dev, uint32_t flags, uint32_t mtu, uint32_t err_limit,
+                         const udpdk_icmp_out_t *o)
+{
+    int rc = icmp_check(c, cfg, bt, meta_dev, flags, mtu, o);
+    if (rc) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    if (c->depth > 1 && (rc = join_pipes(c))) return rc;
+    return icmp_enqueue(c, c->icmp, c->stream, cfg, bt, meta_dev, flags, mtu, err_limit, o);
+}
+
+int udpdk_gpu_icmp_stats(udpdk_gpu_ctx *c, udpdk_icmp_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    IcmpWs &W = c->icmp;
+    if (!W.ran) return -ENOENT;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipMemcpyAsync(W.h_res, W.res, sizeof(IcmpResult), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return icmp_stats_out(W.h_res, st);
+}
+
+int udpdk_gpu_pipe_icmp_reply(udpdk_gpu_ctx *c, int pipe, const udpdk_tx_config_t *cfg,
+                              const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, uint32_t flags,
+                              uint32_t mtu, uint32_t err_limit, const udpdk_icmp_out_t *o)
+{
+    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    int rc = icmp_check(c, cfg, bt, meta_dev, flags, mtu, o);
+    if (rc) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    Pipe &P = c->pipes[pipe];
+    P.dirty = true;
+    if ((rc = icmp_enqueue(c, P.icmp, P.stream, cfg, bt, meta_dev, flags, mtu, err_limit, o))) return rc;
+    // the counts follow on the pipe's stream: udpdk_gpu_pipe_icmp_stats reads them after udpdk_gpu_pipe_wait
+    HIPC(c, hipMemcpyAsync(P.icmp.h_res, P.icmp.res, sizeof(IcmpResult), hipMemcpyDeviceToHost, P.stream));
+    return 0;
+}
+
+int udpdk_gpu_pipe_icmp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_icmp_stats_t *st)
+{
+    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    const IcmpWs &W = c->pipes[pipe].icmp;
+    if (!W.ran) return -ENOENT;
+    return icmp_stats_out(W.h_res, st);
 }
 
 #ifdef UDPDK_STAMPS
