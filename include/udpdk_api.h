@@ -286,9 +286,10 @@ int udpdk_peer_lanes(udpdk_peer_t *peers, uint32_t n);
  * replies queued in chunk order); fragments (the FRAG verdict) and datagrams reassembled from them
  * are not answered, and neither is anything by udpdk_poll_echo. Sharded polls ([gpu] devices with
  * two or more entries) do not answer: there a nonzero flags gives -1 with ENOTSUP, and udpdk_init
- * fails on such an ini. With the loopback port the answers come back as ICMP types 0 and 3, which
- * nothing answers. Returns the flags in force before the call; a negative argument only reads them;
- * a bit outside UDPDK_ICMP_ALL: -1, EINVAL. */
+ * fails on such an ini. With the loopback port the answers come back as ICMP types 0 and 3: nothing
+ * answers them, and with udpdk_config_icmp_errors on a type 3 that quotes a connected socket's
+ * datagram is reported to that socket (ECONNREFUSED). Returns the flags in force before the call; a
+ * negative argument only reads them; a bit outside UDPDK_ICMP_ALL: -1, EINVAL. */
 int udpdk_config_icmp(int flags);
 /* Port-unreachable errors answered per poll (ini: [gpu] icmp_burst = N; default 64, a policy default
  * in the spirit of Linux's icmp_msgs_burst, not a measured value): the first N eligible datagrams
@@ -304,6 +305,44 @@ typedef struct {
     uint64_t echo_replied, unreach_sent, echo_bad, limited, queue_dropped;
 } udpdk_icmp_counts_t;
 int udpdk_icmp_counts(udpdk_icmp_counts_t *counts);
+
+/* ICMP errors received (ini: [gpu] icmp_errors = 0 | 1; default 0: a received ICMP error ends as
+ * NOT_UDP and is forgotten, as in the reference). With 1, and while at least one socket is connected,
+ * udpdk_poll_rx runs udpdk_gpu_icmp_errors (udpdk_gpu.h) after a batch's RX, next to the ICMP answers:
+ * a destination-unreachable message to our address that quotes a datagram a connected socket sent to
+ * its peer, with a hard code (udpdk_gpu_icmp_errno), becomes that socket's pending error, the last
+ * one of a poll in arrival order (RFC 1122 §4.1.3.3; Linux's sk_err):
+ *   - the next udpdk_recvfrom / udpdk_recv / udpdk_sendto / udpdk_send on the socket returns -1 with
+ *     that errno (ECONNREFUSED for a port-unreachable) and clears it. Receive calls check it before
+ *     the ring: datagrams already queued stay queued and the following call returns them. A
+ *     udpdk_recvfrom waiting on an empty ring sees the error and returns.
+ *   - udpdk_getsockopt(s, SOL_SOCKET, SO_ERROR, &int, &len) returns the value and clears it (0: none);
+ *     udpdk_setsockopt of SO_ERROR stays ENOPROTOOPT.
+ *   - udpdk_connect (a new peer, AF_UNSPEC), udpdk_close and udpdk_host_reset clear it.
+ * The one-piece and the chunked poll report (a chunk on its pipe). Not looked at: ICMP that is itself
+ * fragmented (the FRAG verdict) and reassembled datagrams, errors about fragments other than the
+ * first, soft errors (counted, never reported: no IP_RECVERR, no path-MTU handling), anything in
+ * udpdk_poll_echo. Sharded polls do not report: there on = 1 gives -1 with ENOTSUP and udpdk_init
+ * fails on such an ini, as for udpdk_config_icmp. Returns the value in force before the call; a
+ * negative argument only reads it; above 1: -1, EINVAL. */
+int udpdk_config_icmp_errors(int on);
+/* Poller internals (what the stage calls for every reported word; host only, needs no GPU): under
+ * the socket lock, if s is in use, still connected to exactly peer_ip : peer_port (raw) and code is a
+ * hard error, the socket's pending error becomes udpdk_gpu_icmp_errno(code), a later post
+ * overwriting an earlier one, and the call returns 1; otherwise it changes nothing and returns 0
+ * (a udpdk_connect between the poll's peer upload and the post wins). */
+int udpdk_sock_error_post(int s, uint32_t peer_ip, uint16_t peer_port, uint32_t code);
+/* Poller internals (host only, needs no GPU): queue one datagram on socket s's RX ring as a poll
+ * would, from bytes the caller keeps alive until the datagram is received or the socket closed (no
+ * slab is taken). For pollers that deliver from memory of their own and for tests of the receive
+ * calls without a device. 0, or -1 with ENOTSOCK / EBADF / ENOBUFS (ring full). */
+int udpdk_sock_rx_inject(int s, const void *data, uint32_t len, uint32_t src_ip, uint16_t src_port);
+/* Session sums over polls, like udpdk_icmp_counts: the device stage's counts (udpdk_icmp_err_stats_t)
+ * and posted, the posts that took effect. udpdk_host_reset zeroes them. */
+typedef struct {
+    uint64_t errors, msg_bad, quote_bad, soft, no_socket, reported, posted;
+} udpdk_icmp_err_counts_t;
+int udpdk_icmp_err_counts(udpdk_icmp_err_counts_t *counts);
 
 /* Socket slot state (exch_slot_info, udpdk_types.h:40-47) for the GPU TX slot table. */
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots);

@@ -53,7 +53,9 @@ extern "C" {
  *    (still 3: udpdk_gpu_rx_peer_select / udpdk_gpu_rx_peer / udpdk_gpu_rx_peer_stats /
  *    udpdk_gpu_rx_peer_removed were added)
  *    (still 3: udpdk_gpu_icmp_reply / udpdk_gpu_icmp_stats / udpdk_gpu_icmp_geometry /
- *    udpdk_gpu_pipe_icmp_reply / udpdk_gpu_pipe_icmp_stats were added) */
+ *    udpdk_gpu_pipe_icmp_reply / udpdk_gpu_pipe_icmp_stats were added)
+ *    (still 3: udpdk_gpu_icmp_errors / udpdk_gpu_icmp_err_stats / udpdk_gpu_pipe_icmp_errors /
+ *    udpdk_gpu_pipe_icmp_err_stats / udpdk_gpu_icmp_errno were added) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -865,6 +867,81 @@ int udpdk_gpu_pipe_icmp_reply(udpdk_gpu_ctx *ctx, int pipe, const udpdk_tx_confi
                               uint32_t flags, uint32_t mtu, uint32_t err_limit,
                               const udpdk_icmp_out_t *out);
 int udpdk_gpu_pipe_icmp_stats(udpdk_gpu_ctx *ctx, int pipe, udpdk_icmp_stats_t *stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * ICMP errors received: of a finished udpdk_gpu_rx call, the destination-unreachable messages (type
+ * 3) that quote a datagram one of our connected sockets sent to its peer, as one 64-bit word per lane
+ * for the last such hard error in arrival order (Linux: a later error overwrites sk_err). RFC 1122
+ * §4.1.3.3: UDP MUST pass ICMP errors up to the application; this is what connect() on a UDP socket
+ * gives a POSIX program beyond the peer filter (ECONNREFUSED from a dead service instead of a
+ * timeout). The reference has no ICMP and no connect. One more optional stage after RX, reading the
+ * verdict words, the staged frames, the uploaded bind snapshot and a peer table.
+ *
+ * m = meta[i]; tl = the big-endian u16 at frame bytes 16-17; addresses and ports are raw.
+ *   - Candidate by meta: verdict NOT_UDP, UDPDK_META_IP_OK(m), not UDPDK_META_IHL_NE5(m). For any other
+ *     frame no descriptor and no frame byte is read: a batch of UDP to bound ports costs the read
+ *     of meta plus the clearing of err_dev.
+ *   - Frame gate: length[i] >= 42 and offset[i] + length[i] <= frames_bytes (64 bits), else the
+ *     candidate counts as bad_frame and no frame byte is read (meta need not come from this batch).
+ *   - An error to us (counted under errors): byte 23 == 1, byte 34 == 3, bytes 30-33 == our_ip.
+ *     Anything else (echo traffic, other ICMP types, other destinations) is counted nowhere.
+ *   - Message: valid when tl >= 56, 14 + tl <= length[i] and the one's-complement sum of bytes
+ *     [34, 14 + tl) verifies (odd tail zero-padded; Ethernet padding past 14 + tl is not summed);
+ *     else msg_bad. Messages are 36 bytes up to a full MTU (routers quote as much as they can).
+ *   - Quote: valid when byte 42 == 0x45, byte 51 == 17 and the quoted fragment offset is 0
+ *     (be16(bytes 48-49) & 0x1FFF == 0); else quote_bad. The quoted header checksum is not verified
+ *     (Linux does not verify it either). Quoted source: bytes 54-57, destination: 58-61, source
+ *     port: 62-63, destination port: 64-65.
+ *   - Code (byte 35): udpdk_gpu_icmp_errno's table, which is Linux's icmp_err_convert:
+ *       0 ENETUNREACH soft, 1 EHOSTUNREACH soft, 2 ENOPROTOOPT hard, 3 ECONNREFUSED hard,
+ *       4 EMSGSIZE soft (we send with DF clear), 5 EOPNOTSUPP soft, 6 ENETUNREACH hard,
+ *       7 EHOSTDOWN hard, 8 ENONET hard, 9 ENETUNREACH hard, 10 EHOSTUNREACH hard, 11 ENETUNREACH
+ *       soft, 12 EHOSTUNREACH soft, 13-15 EHOSTUNREACH hard, above 15: none, soft.
+ *     A code that is not hard counts as soft and reports nothing.
+ *   - Socket: the snapshot's bindings of the quoted source port in list order; binding b with lane
+ *     l = b.sockfd matches when l < n_lanes, b.ip == the quoted source (or b.ip == 0 and the quoted
+ *     source is our_ip: what an ANY socket sends), peer[l].on, peer[l].ip == the quoted
+ *     destination and peer[l].port == the quoted destination port. Every match is reported: the
+ *     walk does not stop at a binding without reuse (two sockets cannot both own the 5-tuple in
+ *     any case). No match: no_socket.
+ *   - Report: err_dev[l] = max(err_dev[l], ((uint64)(i + 1) << 8) | code) by a 64-bit atomic max,
+ *     so the result does not depend on scheduling. The stage first clears err_dev[0, n_lanes) on
+ *     the same stream; 0 means no error.
+ * The uploaded snapshot must have lane_mask == 0xFFFFFFFF (a lane is a sockfd, as for the peer
+ * filter). peer_dev is [n_lanes], 8-byte aligned; NULL means the context's sticky table from
+ * udpdk_gpu_rx_peer (lanes past what it was given are off), -ENOENT when that stage is off.
+ * -EINVAL with nothing enqueued: a NULL pointer (peer_dev excepted), peer_dev or err_dev not 8-byte
+ * aligned, n_lanes outside 1..UDPDK_GPU_MAX_LANES, frames_bytes >= 2^32, no snapshot uploaded or one
+ * in compat mode. n == 0 clears err_dev and returns 0. Asynchronous on the context stream; joins the
+ * pipes as udpdk_gpu_icmp_reply does. The frames buffer keeps the tailroom contract of udpdk_gpu_rx.
+ * meta is read and never written. The launches are not event-timed.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t errors;     /* type-3 messages to us past the frame gate                          */
+    uint32_t msg_bad;    /* ... with a bad total length or ICMP checksum                       */
+    uint32_t quote_bad;  /* ... whose quote is not an IHL-5, first-fragment IPv4/UDP header    */
+    uint32_t soft;       /* ... with a code that is not a hard error                           */
+    uint32_t no_socket;  /* hard errors that matched no connected socket                       */
+    uint32_t reported;   /* (frame, socket) pairs reported                                     */
+    uint32_t bad_frame;  /* candidate by meta, but length < 42 or out of range: not read       */
+} udpdk_icmp_err_stats_t;
+
+int udpdk_gpu_icmp_errors(udpdk_gpu_ctx *ctx, uint32_t our_ip, const udpdk_rx_batch_t *batch,
+                          const uint32_t *meta_dev, const udpdk_peer_t *peer_dev, uint32_t n_lanes,
+                          uint64_t *err_dev /* [n_lanes] */);
+/* Of the last udpdk_gpu_icmp_errors on the context (-ENOENT when there was none). Synchronises. */
+int udpdk_gpu_icmp_err_stats(udpdk_gpu_ctx *ctx, udpdk_icmp_err_stats_t *stats);
+/* Poller internals: the same stage on pipe `pipe`'s stream (1 .. 3) with that pipe's workspace and
+ * no joins, like udpdk_gpu_pipe_icmp_reply; the counts are copied to pinned memory on the same
+ * stream. udpdk_gpu_pipe_icmp_err_stats reads them without synchronising: they are those of the
+ * pipe's last stage once udpdk_gpu_pipe_wait has returned (-ENOENT: the pipe never ran one). */
+int udpdk_gpu_pipe_icmp_errors(udpdk_gpu_ctx *ctx, int pipe, uint32_t our_ip,
+                               const udpdk_rx_batch_t *batch, const uint32_t *meta_dev,
+                               const udpdk_peer_t *peer_dev, uint32_t n_lanes, uint64_t *err_dev);
+int udpdk_gpu_pipe_icmp_err_stats(udpdk_gpu_ctx *ctx, int pipe, udpdk_icmp_err_stats_t *stats);
+/* The errno of destination-unreachable code `code` (0: none, codes above 15) and, when hard is not
+ * NULL, whether the error is hard (1) or soft (0). Host only. */
+int udpdk_gpu_icmp_errno(uint32_t code, int *hard);
 
 /* ---------------------------------------------------------------------------------------------
  * Timing (for bench.py / the roofline): on every `enable`-th udpdk_gpu_rx call (0 = off, 1 =

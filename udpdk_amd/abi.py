@@ -208,6 +208,20 @@ class IcmpCounts(C.Structure):
                 ("limited", C.c_uint64), ("queue_dropped", C.c_uint64)]
 
 
+class IcmpErrStats(C.Structure):
+    """udpdk_icmp_err_stats_t"""
+    _fields_ = [("errors", C.c_uint32), ("msg_bad", C.c_uint32), ("quote_bad", C.c_uint32), ("soft", C.c_uint32),
+                ("no_socket", C.c_uint32), ("reported", C.c_uint32), ("bad_frame", C.c_uint32)]
+
+
+class IcmpErrCounts(C.Structure):
+    """udpdk_icmp_err_counts_t (udpdk_api.h)"""
+    _fields_ = [("errors", C.c_uint64), ("msg_bad", C.c_uint64), ("quote_bad", C.c_uint64), ("soft", C.c_uint64),
+                ("no_socket", C.c_uint64), ("reported", C.c_uint64), ("posted", C.c_uint64)]
+
+
+ICMP_ERR_STATS = ("errors", "msg_bad", "quote_bad", "soft", "no_socket", "reported", "bad_frame")
+
 # name -> (restype, argtypes); every symbol the headers declare
 _P = C.c_void_p
 _PROTOS = {
@@ -289,6 +303,11 @@ _PROTOS = {
     "udpdk_gpu_pipe_icmp_reply": (C.c_int, [_P, C.c_int, C.POINTER(TxConfig), C.POINTER(RxBatch), _P, C.c_uint32,
                                             C.c_uint32, C.c_uint32, C.POINTER(IcmpOut)]),
     "udpdk_gpu_pipe_icmp_stats": (C.c_int, [_P, C.c_int, C.POINTER(IcmpStats)]),
+    "udpdk_gpu_icmp_errors": (C.c_int, [_P, C.c_uint32, C.POINTER(RxBatch), _P, _P, C.c_uint32, _P]),
+    "udpdk_gpu_icmp_err_stats": (C.c_int, [_P, C.POINTER(IcmpErrStats)]),
+    "udpdk_gpu_pipe_icmp_errors": (C.c_int, [_P, C.c_int, C.c_uint32, C.POINTER(RxBatch), _P, _P, C.c_uint32, _P]),
+    "udpdk_gpu_pipe_icmp_err_stats": (C.c_int, [_P, C.c_int, C.POINTER(IcmpErrStats)]),
+    "udpdk_gpu_icmp_errno": (C.c_int, [C.c_uint32, C.POINTER(C.c_int)]),
     "udpdk_gpu_timing_enable": (C.c_int, [_P, C.c_int]),
     "udpdk_gpu_timing_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "udpdk_gpu_rx_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
@@ -333,6 +352,10 @@ _PROTOS = {
     "udpdk_config_icmp": (C.c_int, [C.c_int]),
     "udpdk_config_icmp_burst": (C.c_int, [C.c_int]),
     "udpdk_icmp_counts": (C.c_int, [C.POINTER(IcmpCounts)]),
+    "udpdk_config_icmp_errors": (C.c_int, [C.c_int]),
+    "udpdk_sock_error_post": (C.c_int, [C.c_int, C.c_uint32, C.c_uint16, C.c_uint32]),
+    "udpdk_icmp_err_counts": (C.c_int, [C.POINTER(IcmpErrCounts)]),
+    "udpdk_sock_rx_inject": (C.c_int, [C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint16]),
     "udpdk_tx_pending": (C.c_uint64, []),
     "udpdk_tx_dropped": (C.c_uint64, []),
     "udpdk_rx_nobufs": (C.c_uint64, []),
@@ -922,6 +945,46 @@ def icmp_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, meta, *, flags: i
             x.free()
 
 
+def icmp_errno(code: int) -> tuple[int, int]:
+    """udpdk_gpu_icmp_errno: (errno, hard) of a destination-unreachable code."""
+    h = C.c_int(-1)
+    return lib().udpdk_gpu_icmp_errno(code, C.byref(h)), h.value
+
+
+def icmp_err_run(ctx: GpuContext, our_ip: int, b: RxDeviceBatch, meta, peers, n_lanes: int, *, n=None,
+                 pipe: int = 0, pad: int = 8, err_ptr=None, peer_ptr=None):
+    """udpdk_gpu_icmp_errors (pipe 0) or udpdk_gpu_pipe_icmp_errors + udpdk_gpu_pipe_wait over host verdict
+    words. peers: PEER_DTYPE records uploaded as peer_dev, or None for the context's sticky table.
+    Returns a dict: rc of the call, rc and struct of the stats call, and err: the words as downloaded,
+    `pad` longer than the call may write and pre-filled with 0xA5 bytes. err_ptr / peer_ptr replace
+    the device pointers (argument checks)."""
+    meta = np.ascontiguousarray(meta, np.uint32)
+    n = b.n if n is None else n
+    bufs = [ctx.upload(meta), ctx.upload(np.full(8 * (n_lanes + pad), 0xA5, np.uint8))]
+    if peers is not None:
+        bufs.append(ctx.upload(np.ascontiguousarray(peers, PEER_DTYPE).view(np.uint8)))
+    try:
+        bt = RxBatch(b.frames.ptr, b.frames_bytes, b.offset.ptr, b.length.ptr,
+                     b.ptype.ptr if b.ptype is not None else None, n)
+        pp = C.c_void_p(peer_ptr if peer_ptr is not None else (bufs[2].ptr if peers is not None else None))
+        ep = C.c_void_p(bufs[1].ptr if err_ptr is None else err_ptr)
+        st = IcmpErrStats()
+        if pipe:
+            rc = lib().udpdk_gpu_pipe_icmp_errors(ctx.handle, pipe, our_ip, C.byref(bt), C.c_void_p(bufs[0].ptr), pp,
+                                                  n_lanes, ep)
+            _check(lib().udpdk_gpu_pipe_wait(ctx.handle, pipe), "udpdk_gpu_pipe_wait")
+            src = lib().udpdk_gpu_pipe_icmp_err_stats(ctx.handle, pipe, C.byref(st))
+        else:
+            rc = lib().udpdk_gpu_icmp_errors(ctx.handle, our_ip, C.byref(bt), C.c_void_p(bufs[0].ptr), pp, n_lanes, ep)
+            src = lib().udpdk_gpu_icmp_err_stats(ctx.handle, C.byref(st))
+        ctx.sync()
+        return {"rc": rc, "stats_rc": src, "stats": {k: getattr(st, k) for k in ICMP_ERR_STATS},
+                "err": ctx.download(bufs[1], np.uint64, n_lanes + pad)}
+    finally:
+        for x in bufs:
+            x.free()
+
+
 @dataclass
 class DevRef:
     """A device pointer the context owns (no free)."""
@@ -1153,6 +1216,26 @@ class HostApi:
     def icmp_counts(self) -> IcmpCounts:
         c = IcmpCounts()
         _check(lib().udpdk_icmp_counts(C.byref(c)), "udpdk_icmp_counts")
+        return c
+
+    def config_icmp_errors(self, on: int) -> int:
+        """Received ICMP errors as pending socket errors (udpdk_config_icmp_errors): returns the previous
+        setting; a negative `on` only reads it."""
+        return self.L.udpdk_config_icmp_errors(int(on))
+
+    def sock_error_post(self, s: int, ip: str | int, port_host: int, code: int) -> int:
+        """udpdk_sock_error_post against the peer ip : port."""
+        return self.L.udpdk_sock_error_post(s, raw_ip(ip) if isinstance(ip, str) else ip, raw_port(port_host), code)
+
+    def rx_inject(self, s: int, payload: bytes, ip: str, port_host: int) -> int:
+        """udpdk_sock_rx_inject; the bytes are kept alive by this object."""
+        buf = C.create_string_buffer(payload, max(1, len(payload)))
+        self._injected = getattr(self, "_injected", []) + [buf]
+        return self.L.udpdk_sock_rx_inject(s, buf, len(payload), raw_ip(ip), raw_port(port_host))
+
+    def icmp_err_counts(self) -> IcmpErrCounts:
+        c = IcmpErrCounts()
+        _check(self.L.udpdk_icmp_err_counts(C.byref(c)), "udpdk_icmp_err_counts")
         return c
 
     def tx_pending(self) -> int:

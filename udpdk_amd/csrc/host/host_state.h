@@ -92,6 +92,7 @@ struct h_slot {                  /* exch_slot_info (udpdk_types.h:40-47) + bind 
     uint8_t  connected;          /* udpdk_connect: the socket has a peer (always bound then)        */
     uint16_t peer_port;          /* raw */
     uint32_t peer_ip;            /* raw */
+    atomic_int so_error;         /* pending ICMP error (udpdk_sock_error_post): an errno, 0 = none     */
     struct h_ring rx;
     struct h_txq  tx;
 };
@@ -257,6 +258,15 @@ struct h_state {
     udpdk_icmp_counts_t icmp_counts;
     void     *ic_out_d, *ic_idx_d, *ic_h;
     uint64_t  ic_out_d_cap, ic_idx_d_cap, ic_h_cap;
+    /* ICMP errors received (rx_icmp_err.c): [gpu] icmp_errors / udpdk_config_icmp_errors (0: a poll
+     * enqueues what it always did), the session's counts (under lock) and the peer records the
+     * contexts hold (h_peer_apply: what an error is posted against); work buffers, grow-only, one
+     * word per lane: the device output and its pinned readback */
+    uint32_t  icmp_errors;
+    udpdk_icmp_err_counts_t icmp_err_counts;
+    udpdk_peer_t peer_up[UDPDK_MAX_SOCKETS];
+    void     *ie_d, *ie_h;
+    uint64_t  ie_d_cap, ie_h_cap;
     /* poller thread (udpdk_port_attach) */
     pthread_t poller;
     atomic_int poller_run;
@@ -325,5 +335,13 @@ void h_icmp_buffers_free(void);
 uint32_t h_icmp_budget(void);
 int  h_icmp_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const uint32_t *meta_dev,
                   uint32_t *budget);
+
+
+/* rx_icmp_err.c */
+void h_icmp_err_reset(void);              /* under g_udpdk.lock */
+void h_icmp_err_buffers_free(void);
+int  h_sock_error_post_locked(int s, uint32_t peer_ip, uint16_t peer_port, uint32_t code);
+int  h_sock_error_take(int s);            /* the pending error, cleared (0: none) */
+int  h_icmp_err_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const uint32_t *meta_dev);
 
 #endif

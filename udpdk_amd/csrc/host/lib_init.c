@@ -44,6 +44,7 @@ static void h_config_defaults(void)
     g_udpdk.reuseport = UDPDK_REUSEPORT_FANOUT;   /* every reuse socket gets a clone, as in the reference */
     g_udpdk.icmp_flags = 0;            /* no ICMP answers, as in the reference */
     g_udpdk.icmp_burst = H_ICMP_BURST_DEFAULT;
+    g_udpdk.icmp_errors = 0;           /* received ICMP errors are forgotten, as in the reference */
     g_udpdk.arena_bytes_max = 4ull << 30;
     g_udpdk.arena_count_max = 1024;
     g_udpdk.port_spec[0] = g_udpdk.port_peer[0] = 0;
@@ -72,6 +73,7 @@ void udpdk_host_reset(void)
     h_btable_reset();
     h_sockets_reset();
     h_icmp_reset();
+    h_icmp_err_reset();
     pthread_mutex_unlock(&g_udpdk.tx_lock);
     atomic_store(&g_udpdk.interrupted, 0);
     g_udpdk.snap_version = UINT64_MAX;
@@ -81,6 +83,7 @@ void udpdk_host_reset(void)
     g_udpdk.reuseport = UDPDK_REUSEPORT_FANOUT;
     g_udpdk.icmp_flags = 0;
     g_udpdk.icmp_burst = H_ICMP_BURST_DEFAULT;
+    g_udpdk.icmp_errors = 0;
     pthread_mutex_unlock(&g_udpdk.lock);
 }
 
@@ -324,6 +327,11 @@ static int h_load_ini(const char *path)
             const long b = strtol(v, &e, 0);
             if (e == v || *e || b < -1 || b > INT32_MAX) { rc = -1; break; }
             g_udpdk.icmp_burst = (int32_t)b;
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "icmp_errors")) {
+            /* 1: received ICMP errors become the pending errors of connected sockets (SO_ERROR);
+             * 0 (default); checked against [gpu] devices once the file is read */
+            if (!strcmp(v, "0") || !strcmp(v, "1")) g_udpdk.icmp_errors = (uint32_t)(v[0] - '0');
+            else { rc = -1; break; }
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port")) {
             snprintf(g_udpdk.port_spec, sizeof(g_udpdk.port_spec), "%s", v);
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port_peer")) {
@@ -338,6 +346,8 @@ static int h_load_ini(const char *path)
     fclose(f);
     /* sharded polls do not answer (udpdk_config_icmp: ENOTSUP) */
     if (!rc && g_udpdk.icmp_flags && g_udpdk.n_shards > 1) rc = -1;
+    /* ... and do not report received errors (udpdk_config_icmp_errors: ENOTSUP, here as -2) */
+    if (!rc && g_udpdk.icmp_errors && g_udpdk.n_shards > 1) rc = -2;
     return rc;
 }
 
@@ -351,7 +361,8 @@ int udpdk_init(int argc, char *argv[])
     }
     if (!cfg) { errno = EINVAL; return -1; }       /* config file is mandatory (args.c:150-155) */
     if (!g_udpdk.gpu) h_config_defaults();
-    if (h_load_ini(cfg)) { errno = EINVAL; return -1; }
+    const int lrc = h_load_ini(cfg);
+    if (lrc) { errno = lrc == -2 ? ENOTSUP : EINVAL; return -1; }
     if (g_udpdk.gpu) return 0;
     int rc = udpdk_gpu_ctx_create(g_udpdk.gpu_device, g_udpdk.gpu_max_frames,
                                   g_udpdk.gpu_max_lanes, &g_udpdk.gpu);
@@ -443,6 +454,7 @@ void udpdk_cleanup(void)
     h_tx_buffers_free();
     h_echo_buffers_free();
     h_icmp_buffers_free();
+    h_icmp_err_buffers_free();
     h_arenas_free_all();
     g_udpdk.frag_ready = 0;
     h_shards_destroy();

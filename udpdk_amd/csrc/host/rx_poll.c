@@ -267,7 +267,7 @@ int h_peer_apply(void)
     if (want && g_udpdk.peer_applied && g_udpdk.peer_version_applied == g_udpdk.peer_version &&
         g_udpdk.peer_snap_version == g_udpdk.snap_version)
         return 0;
-    static udpdk_peer_t peers[UDPDK_MAX_SOCKETS];
+    udpdk_peer_t *peers = g_udpdk.peer_up;   /* kept: what a received ICMP error is posted against */
     uint32_t n = 0, on = 0;
     if (want) {
         n = g_udpdk.snap_lanes < UDPDK_MAX_SOCKETS ? g_udpdk.snap_lanes : UDPDK_MAX_SOCKETS;
@@ -1236,6 +1236,8 @@ static int h_poll_chunked(const uint8_t *frames, uint64_t frames_bytes, const ui
         const uint64_t nfrag = C->st.counters[UDPDK_V_FRAG];
         /* [gpu] icmp: the chunk's answers, on its pipe, before reassembly touches the frames */
         if (h_icmp_stage(g, h_pipe_of(k), &staged, meta_dev, &icmp_budget)) { err = errno; break; }
+        /* [gpu] icmp_errors: the chunk's ICMP errors for connected sockets, on its pipe */
+        if (h_icmp_err_stage(g, h_pipe_of(k), &staged, meta_dev)) { err = errno; break; }
         if (h_frag_pass(&staged, meta_dev, nfrag, lanes, maxfan, 1, &rb, &nd)) { err = errno; break; }
         CPROF_T(t1); CPROF_ADD(4, t0, t1); t0 = t1;
         const uint32_t *floff = nd ? g_udpdk.fr_loff : NULL;
@@ -1375,6 +1377,9 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
          * udpdk_tx_drain, before reassembly touches the frames (nothing is enqueued with flags 0) */
         uint32_t icmp_budget = h_icmp_budget();
         if (h_icmp_stage(g, 0, &staged, meta_dev, &icmp_budget)) goto out;
+        /* [gpu] icmp_errors: received ICMP errors become the pending errors of connected sockets
+         * (nothing is enqueued with the switch off or no socket connected) */
+        if (h_icmp_err_stage(g, 0, &staged, meta_dev)) goto out;
         const int inplace = nfrag && h_desc_disjoint(offset, length, n, frames_bytes);
         if (h_frag_pass(&staged, meta_dev, nfrag, lanes, maxfan, inplace, &rb, &nd)) goto out;
     }

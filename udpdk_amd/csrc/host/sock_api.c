@@ -69,6 +69,23 @@ int h_ring_push_bulk(struct h_ring *r, const struct h_dgram *d, uint32_t n)
     return 0;
 }
 
+/* One datagram into socket s's ring from caller-owned bytes (udpdk_api.h: poller internals). */
+int udpdk_sock_rx_inject(int s, const void *data, uint32_t len, uint32_t src_ip, uint16_t src_port)
+{
+    if (!h_valid_fd(s)) { errno = ENOTSOCK; return -1; }
+    pthread_mutex_lock(&g_udpdk.lock);                 /* the poller's lock: one producer at a time */
+    int rc = -1;
+    if (!g_udpdk.slots[s].used) {
+        errno = EBADF;
+    } else {
+        const struct h_dgram d = {data, len, src_ip, src_port, NULL};
+        rc = h_ring_push_bulk(&g_udpdk.slots[s].rx, &d, 1);
+        if (rc) errno = ENOBUFS;
+    }
+    pthread_mutex_unlock(&g_udpdk.lock);
+    return rc;
+}
+
 /* ---- payload slabs ------------------------------------------------------------------------ */
 #define H_ARENA_FREE_KEEP 32     /* free slabs kept for reuse; the rest go back to the runtime
                                   * (a pipelined poll makes a slab per chunk: with 8 kept, every
@@ -292,6 +309,7 @@ int udpdk_socket(int domain, int type, int protocol)
             sl->ip = 0;
             sl->udp_port = 0;
             sl->connected = 0;
+            atomic_store(&sl->so_error, 0);
             sl->prev = sl->next = -1;
             g_udpdk.n_active++;
             ret = s;
@@ -314,6 +332,13 @@ static int h_sockopt_check(int s, int level, int optname, const void *optval, co
 
 int udpdk_getsockopt(int s, int level, int optname, void *optval, socklen_t *optlen)
 {
+    if (optname == SO_ERROR && level == SOL_SOCKET && h_valid_fd(s) && g_udpdk.slots[s].used) {
+        /* the pending ICMP error (udpdk_config_icmp_errors), cleared by the read; 0: none */
+        if (!optval || !optlen) { errno = EFAULT; return -1; }
+        *(int *)optval = h_sock_error_take(s);
+        *optlen = sizeof(int);
+        return 0;
+    }
     if (h_sockopt_check(s, level, optname, optval, optlen)) return -1;
     /* bitwise test of the option value: SO_REUSEPORT (15) contains SO_REUSEADDR (2), so
      * setting REUSEPORT reads back REUSEADDR = 1 as in the reference */
@@ -379,6 +404,7 @@ int udpdk_close(int s)
     sl->tx.e = NULL;
     sl->tx.head = sl->tx.tail = 0;
     pthread_mutex_unlock(&g_udpdk.tx_lock);
+    atomic_store(&sl->so_error, 0);
     if (sl->connected) {                       /* the peer goes with the socket */
         sl->connected = 0;
         g_udpdk.n_connected--;
@@ -426,6 +452,7 @@ ssize_t udpdk_sendto(int s, const void *buf, size_t len, int flags,
     if (s < 0 || s >= UDPDK_MAX_SOCKETS) { errno = ENOTSOCK; return -1; }
     if (!g_udpdk.slots[s].used) { errno = EBADF; return -1; }
     if (flags != 0) { errno = EINVAL; return -1; }
+    { const int e = h_sock_error_take(s); if (e) { errno = e; return -1; } }   /* pending ICMP error */
     struct sockaddr_in peer;
     if (!dest) {
         /* a connected socket's peer (udpdk_connect); unconnected: EINVAL as ever */
@@ -492,8 +519,10 @@ ssize_t udpdk_recvfrom(int s, void *buf, size_t len, int flags,
         return -1;
     }
     const uint32_t h = atomic_load_explicit(&r->head, memory_order_relaxed);
+    /* a pending ICMP error is reported before ring data, which stays queued for the next call */
+    int perr = h_sock_error_take(s);
     /* busy wait like udpdk_syscall.c:424-426; datagrams arrive from the poller (udpdk_poll_rx) */
-    while (atomic_load_explicit(&r->tail, memory_order_acquire) == h) {
+    while (!perr && atomic_load_explicit(&r->tail, memory_order_acquire) == h) {
         const int intr = atomic_load_explicit(&g_udpdk.interrupted, memory_order_relaxed);
         if (intr || atomic_load_explicit(&r->closing, memory_order_relaxed)) {
             atomic_fetch_sub_explicit(&r->busy, 1, memory_order_release);
@@ -501,6 +530,12 @@ ssize_t udpdk_recvfrom(int s, void *buf, size_t len, int flags,
             return -1;
         }
         sched_yield();
+        perr = h_sock_error_take(s);
+    }
+    if (perr) {
+        atomic_fetch_sub_explicit(&r->busy, 1, memory_order_release);
+        errno = perr;
+        return -1;
     }
     const struct h_dgram d = r->e[h % UDPDK_RX_RING_SIZE];
     if (src_addr && addrlen) {
@@ -562,6 +597,7 @@ int udpdk_connect(int s, const struct sockaddr *addr, socklen_t addrlen)
     if (!sl->used) {
         errno = EBADF;
     } else if (addr->sa_family == AF_UNSPEC) {             /* dissolve the association */
+        atomic_store(&sl->so_error, 0);                    /* an error about the old peer goes with it */
         if (sl->connected) {
             sl->connected = 0;
             g_udpdk.n_connected--;
@@ -574,6 +610,7 @@ int udpdk_connect(int s, const struct sockaddr *addr, socklen_t addrlen)
         sl->connected = 1;
         sl->peer_ip = in->sin_addr.s_addr;
         sl->peer_port = in->sin_port;                      /* raw network-order value */
+        atomic_store(&sl->so_error, 0);
         g_udpdk.peer_version++;                            /* the next poll uploads the table */
         ret = 0;
     }

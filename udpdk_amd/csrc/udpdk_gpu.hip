@@ -23,6 +23,7 @@
 #include "rx_balance.h"
 #include "rx_peer.h"
 #include "icmp_reply.h"
+#include "icmp_error.h"
 #include "rss_host.h"
 
 using namespace udpdk;
@@ -94,6 +95,14 @@ struct IcmpWs {
     bool ran = false;                                 // a stage was enqueued (udpdk_gpu_icmp_stats)
 };
 
+// Workspace of the ICMP error stage (icmp_error.hip): its counters. One for the context stream
+// (udpdk_gpu_icmp_errors) and one per pipe (udpdk_gpu_pipe_icmp_errors).
+struct IcmpErrWs {
+    IcmpErrResult *res = nullptr; size_t res_cap = 0;
+    IcmpErrResult *h_res = nullptr; size_t h_res_cap = 0;  // pinned mirror
+    bool ran = false;                                 // a stage was enqueued (udpdk_gpu_icmp_err_stats)
+};
+
 // One RX pipe = a stream and the per-call workspace. With pipelining depth d > 1, consecutive
 // udpdk_gpu_rx calls rotate over d pipes, so one batch's prologue, tail and compaction overlap
 // the other batches' streaming phases (the calls are independent: distinct batches and output
@@ -136,6 +145,7 @@ struct Pipe {
     udpdk_rx_batch_t staged{};                // device view of the last host batch staged here
     const uint32_t *staged_meta = nullptr;    // and its verdict words
     IcmpWs icmp;                              // udpdk_gpu_pipe_icmp_reply on this pipe's stream
+    IcmpErrWs icmp_err;                       // udpdk_gpu_pipe_icmp_errors on this pipe's stream
 };
 constexpr int MAX_PIPES = 4;
 constexpr size_t FUSE_BYTES = 128u * UDPDK_FUSE_LINES;   // one 128-B line per fan-in / repair word
@@ -197,6 +207,7 @@ struct udpdk_gpu_ctx {
     FilterWs *peer_last = nullptr;            // the last peer filter run (udpdk_gpu_rx_peer_stats)
     ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
     IcmpWs icmp;                              // udpdk_gpu_icmp_reply (the context stream)
+    IcmpErrWs icmp_err;                       // udpdk_gpu_icmp_errors (the context stream)
 
     unsigned long long *dbg = nullptr;        // diagnostic stamp buffer (UDPDK_STAMPS builds)
     Reasm *reasm = nullptr;                   // udpdk_gpu_frag_table_create
@@ -506,6 +517,12 @@ int udpdk_gpu_ctx_destroy(udpdk_gpu_ctx *c)
     for (IcmpWs *W : iw) {
         void *pd[] = {W->cand, W->row, W->bbase, W->res};
         for (void *p : pd) if (p) (void)hipFree(p);
+        if (W->h_res) (void)hipHostFree(W->h_res);
+    }
+    IcmpErrWs *ew[MAX_PIPES + 1] = {&c->icmp_err};
+    for (int i = 0; i < MAX_PIPES; ++i) ew[i + 1] = &c->pipes[i].icmp_err;
+    for (IcmpErrWs *W : ew) {
+        if (W->res) (void)hipFree(W->res);
         if (W->h_res) (void)hipHostFree(W->h_res);
     }
     for (Pipe &P : c->pipes) {
@@ -2209,6 +2226,128 @@ int udpdk_gpu_pipe_icmp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_icmp_stats_t *st
     const IcmpWs &W = c->pipes[pipe].icmp;
     if (!W.ran) return -ENOENT;
     return icmp_stats_out(W.h_res, st);
+}
+
+namespace {
+
+// Argument checks of udpdk_gpu_icmp_errors and its pipe form: nothing is enqueued unless all pass.
+int icmp_err_check(const udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const uint32_t *meta_dev,
+                   const udpdk_peer_t *peer_dev, uint32_t n_lanes, const uint64_t *err_dev)
+{
+    if (!c || !bt || !meta_dev || !err_dev) return -EINVAL;
+    if (((uintptr_t)peer_dev & 7u) != 0 || ((uintptr_t)err_dev & 7u) != 0) return -EINVAL;
+    if (n_lanes == 0 || n_lanes > UDPDK_GPU_MAX_LANES) return -EINVAL;
+    if (bt->frames_bytes >= (1ull << 32)) return -EINVAL;
+    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
+    if (!c->have_snapshot || c->lane_mask != 0xFFFFFFFFu) return -EINVAL;   // compat mode: a lane is not a sockfd
+    if (!peer_dev && !c->peer_on) return -ENOENT;                          // no sticky table in force
+    return 0;
+}
+
+// The stage (icmp_error.hip) on stream st with workspace W: clear, scan.
+int icmp_err_enqueue(udpdk_gpu_ctx *c, IcmpErrWs &W, hipStream_t st, uint32_t our_ip, const udpdk_rx_batch_t *bt,
+                     const uint32_t *meta_dev, const udpdk_peer_t *peer_dev, uint32_t n_lanes, uint64_t *err_dev)
+{
+    int rc;
+    if ((rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(IcmpErrResult))) ||
+        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(IcmpErrResult))))
+        return rc;
+    unsigned long long *err = reinterpret_cast<unsigned long long *>(err_dev);
+    hipLaunchKernelGGL(icmp_err_clear, dim3(ceil_div(std::max(n_lanes, ICMP_ERR_ROW + 1u), (uint32_t)ICMP_ERR_BLOCK)),
+                       dim3(ICMP_ERR_BLOCK), 0, st, err, n_lanes, W.res);
+    HIPC(c, hipGetLastError());
+    W.ran = true;
+    if (!bt->n) return 0;
+    IcmpErrArgs ea;
+    ea.frames = bt->frames_dev;
+    ea.offset = bt->offset_dev;
+    ea.length = bt->length_dev;
+    ea.meta = meta_dev;
+    ea.port_tab = c->port_tab;
+    ea.binds = c->binds;
+    // the sticky table holds max_lanes records, off past what udpdk_gpu_rx_peer was given
+    ea.peer = peer_dev ? reinterpret_cast<const uint2 *>(peer_dev) : c->peer_tab;
+    ea.err = err;
+    ea.res = W.res;
+    ea.n = bt->n;
+    ea.frames_bytes = (uint32_t)bt->frames_bytes;
+    ea.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+    ea.our_ip = our_ip;
+    ea.n_lanes = n_lanes;
+    ea.peer_n = peer_dev ? n_lanes : c->max_lanes;
+    hipLaunchKernelGGL(icmp_err_scan, dim3(ceil_div(bt->n, ICMP_ERR_TILE)), dim3(ICMP_ERR_BLOCK), 0, st, ea);
+    HIPC(c, hipGetLastError());
+    return 0;
+}
+
+void icmp_err_stats_out(const IcmpErrResult *r, udpdk_icmp_err_stats_t *st)
+{
+    st->errors = r->c[ICMP_X_ERRORS];
+    st->msg_bad = r->c[ICMP_X_MSG_BAD];
+    st->quote_bad = r->c[ICMP_X_QUOTE_BAD];
+    st->soft = r->c[ICMP_X_SOFT];
+    st->no_socket = r->c[ICMP_X_NO_SOCKET];
+    st->reported = r->c[ICMP_X_REPORTED];
+    st->bad_frame = r->c[ICMP_X_BAD_FRAME];
+}
+
+} // namespace
+
+int udpdk_gpu_icmp_errors(udpdk_gpu_ctx *c, uint32_t our_ip, const udpdk_rx_batch_t *bt, const uint32_t *meta_dev,
+                          const udpdk_peer_t *peer_dev, uint32_t n_lanes, uint64_t *err_dev)
+{
+    int rc = icmp_err_check(c, bt, meta_dev, peer_dev, n_lanes, err_dev);
+    if (rc) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    if (c->depth > 1 && (rc = join_pipes(c))) return rc;
+    return icmp_err_enqueue(c, c->icmp_err, c->stream, our_ip, bt, meta_dev, peer_dev, n_lanes, err_dev);
+}
+
+int udpdk_gpu_icmp_err_stats(udpdk_gpu_ctx *c, udpdk_icmp_err_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    IcmpErrWs &W = c->icmp_err;
+    if (!W.ran) return -ENOENT;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipMemcpyAsync(W.h_res, W.res, sizeof(IcmpErrResult), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    icmp_err_stats_out(W.h_res, st);
+    return 0;
+}
+
+int udpdk_gpu_pipe_icmp_errors(udpdk_gpu_ctx *c, int pipe, uint32_t our_ip, const udpdk_rx_batch_t *bt,
+                               const uint32_t *meta_dev, const udpdk_peer_t *peer_dev, uint32_t n_lanes,
+                               uint64_t *err_dev)
+{
+    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    int rc = icmp_err_check(c, bt, meta_dev, peer_dev, n_lanes, err_dev);
+    if (rc) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    Pipe &P = c->pipes[pipe];
+    P.dirty = true;
+    if ((rc = icmp_err_enqueue(c, P.icmp_err, P.stream, our_ip, bt, meta_dev, peer_dev, n_lanes, err_dev))) return rc;
+    // the counts follow on the pipe's stream: udpdk_gpu_pipe_icmp_err_stats reads them after udpdk_gpu_pipe_wait
+    HIPC(c, hipMemcpyAsync(P.icmp_err.h_res, P.icmp_err.res, sizeof(IcmpErrResult), hipMemcpyDeviceToHost, P.stream));
+    return 0;
+}
+
+int udpdk_gpu_pipe_icmp_err_stats(udpdk_gpu_ctx *c, int pipe, udpdk_icmp_err_stats_t *st)
+{
+    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    const IcmpErrWs &W = c->pipes[pipe].icmp_err;
+    if (!W.ran) return -ENOENT;
+    icmp_err_stats_out(W.h_res, st);
+    return 0;
+}
+
+int udpdk_gpu_icmp_errno(uint32_t code, int *hard)
+{
+    // Linux's icmp_err_convert (net/ipv4/icmp.c): errno and whether the error is fatal
+    static const int err[16] = {ENETUNREACH, EHOSTUNREACH, ENOPROTOOPT, ECONNREFUSED, EMSGSIZE, EOPNOTSUPP,
+                                ENETUNREACH, EHOSTDOWN, ENONET, ENETUNREACH, EHOSTUNREACH, ENETUNREACH,
+                                EHOSTUNREACH, EHOSTUNREACH, EHOSTUNREACH, EHOSTUNREACH};
+    if (hard) *hard = code < 16u ? (int)((ICMP_ERR_HARD_MASK >> code) & 1u) : 0;
+    return code < 16u ? err[code] : 0;
 }
 
 #ifdef UDPDK_STAMPS
