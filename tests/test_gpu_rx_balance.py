@@ -108,6 +108,27 @@ def test_entry_counts(bctx, d):
         free(db)
 
 
+def test_workspace_grows_and_is_reused():
+    """A fresh context's first three calls: one tile, then three (the workspace has to grow), then
+    one again (the larger workspace is reused, with the second call's rows, masks and choices
+    beyond the live ones); lanes and stats exact after each."""
+    ctx = abi.GpuContext(0, max_frames=1 << 12, max_lanes=8)
+    try:
+        for step, d in enumerate((64, 2 * E + 1, 64)):
+            a, r = divmod(d, 3)
+            dports = np.array([PA] * a + [PB] * r + [PX])
+            b = flows(len(dports), 900 + step, dports[np.random.default_rng(step).permutation(len(dports))])
+            db, meta, loff, lpkt = rx(ctx, LISTS_AB, b, 4, d)
+            try:
+                assert int(loff[4]) == d
+                m = check(ctx, LISTS_AB, b, db, meta, loff, lpkt, [1, 1, 1, 0], f"step {step} d={d}")
+                assert m.kept == a + r and m.balanced == a
+            finally:
+                free(db)
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("n", [1, T - 1, T, T + 1])
 def test_frame_counts(bctx, n):
     lists = group(PA, 2)

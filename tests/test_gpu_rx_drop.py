@@ -70,6 +70,20 @@ def test_entry_counts(gpu_ctx, d):
             assert 0 < m.removed < d
 
 
+def test_workspace_grows_and_is_reused():
+    """A fresh context's first three calls: one tile, then three (the workspace has to grow), then
+    one again (the larger workspace is reused, with the second call's rows and masks beyond the
+    live ones); lanes and stats exact after each."""
+    ctx = abi.GpuContext(0, max_frames=1 << 12, max_lanes=8)
+    try:
+        for step, d in enumerate((64, 2 * E + 1, 64)):
+            meta, off, pkt = synth(900 + step, d, 7)
+            m = check(ctx, meta, off, pkt, 15, f"step {step} d={d}")
+            assert 0 < m.removed < d
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("n_lanes", [1, 2, 7, 4096, 16384])
 @pytest.mark.parametrize("d", [5000, 40000])
 def test_lane_counts(gpu_ctx, n_lanes, d):

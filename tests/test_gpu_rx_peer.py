@@ -82,6 +82,27 @@ def test_entry_counts_one_lane(pctx, d):
         free(db)
 
 
+def test_workspace_grows_and_is_reused():
+    """A fresh context's first three calls: one tile, then three (the workspace has to grow), then
+    one again (the larger workspace is reused, with the second call's rows and masks beyond the
+    live ones); lanes and stats exact after each."""
+    ctx = abi.GpuContext(0, max_frames=1 << 12, max_lanes=8)
+    try:
+        ctx.upload_snapshot(abi.snapshot_from_lists(ONE, 1))
+        for step, d in enumerate((64, 2 * E + 1, 64)):
+            kinds = random_kinds(d, 900 + step)
+            b = kinds_batch(kinds, 900 + step)
+            db = dev(ctx, b)
+            try:
+                loff, lpkt = U.single_lanes(1, [d])
+                m = check(ctx, b, db, loff, lpkt, U.peer_table(1, {0: U.PEER}), f"step {step} d={d}")
+                assert m.kept == sum(k == PEER_F for k in kinds) and m.refused == d - m.kept
+            finally:
+                free(db)
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("pattern", list(PATTERNS))
 def test_patterns_at_chunk_and_tile_edges(pctx, pattern):
     """Each way to differ from the peer, alone, at the first and the last entry of chunks (also the

@@ -51,57 +51,126 @@ struct TimingSet {
     bool used[TIMED_KERNELS];
 };
 
-// Workspace of the lane filter stage (rx_filter.hip), lazily sized: one per pipe for the sticky mode
-// (udpdk_gpu_rx_drop) and one for explicit udpdk_gpu_rx_filter calls.
-struct FilterWs {
-    unsigned long long *mask = nullptr; size_t mask_cap = 0;
-    uint32_t *row = nullptr; size_t row_cap = 0;
-    uint32_t *base = nullptr; size_t base_cap = 0;
-    uint32_t *pkt = nullptr; size_t pkt_cap = 0;      // sticky mode: the filtered set before it
-    uint32_t *off = nullptr; size_t off_cap = 0;      // goes back into the caller's buffers
-    FilterResult *res = nullptr; size_t res_cap = 0;
-    FilterResult *h_res = nullptr; size_t h_res_cap = 0;   // pinned mirror
-    hipStream_t stream = nullptr;                     // of the last run
-    uint32_t out_cap = 0;
+// Device (Pinned = false) or pinned host (Pinned = true) memory of `cap` elements that its holder
+// owns: sized by ensure(), freed by release() (or, at the latest, with the holder). Not copyable:
+// the workspaces below are held by value and pointed at (udpdk_gpu_ctx::flt_last and the like).
+int hip_rc(udpdk_gpu_ctx *c, hipError_t e);    // 0, or -EIO with c->last_err set
+
+template <typename T, bool Pinned>
+struct Buf {
+    T *p = nullptr;
+    size_t cap = 0;                            // elements
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { release(); }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+    // Room for `count` elements. Nothing happens while they fit; otherwise the old memory is freed
+    // (which synchronises the device, so only ever on growth) and exactly `count` are allocated,
+    // not zeroed. On failure the buffer is left empty.
+    int ensure(udpdk_gpu_ctx *c, size_t count, unsigned host_flags = hipHostMallocDefault)
+    {
+        if (cap >= count) return 0;
+        T *old = p;
+        p = nullptr;
+        cap = 0;
+        void *q = nullptr;
+        int rc;
+        if (old && (rc = hip_rc(c, Pinned ? hipHostFree(old) : hipFree(old)))) return rc;
+        if ((rc = hip_rc(c, Pinned ? hipHostMalloc(&q, count * sizeof(T), host_flags) : hipMalloc(&q, count * sizeof(T)))))
+            return rc;
+        p = static_cast<T *>(q);
+        cap = count;
+        return 0;
+    }
+    void release()
+    {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinnedBuf = Buf<T, true>;
+
+template <typename... B> void release_all(B &...b) { (b.release(), ...); }
+
+// A stage's device result and its pinned mirror. Two ways to read it: fetch() copies and waits
+// (the context-stream *_stats calls); enqueue_fetch() leaves the copy on the stage's stream, and
+// the mirror is read once that stream was waited for (the pipe forms).
+template <typename R>
+struct ResultSlot {
+    DevBuf<R> dev;
+    PinnedBuf<R> host;
+    bool ran = false;                          // a stage was enqueued (-ENOENT from *_stats until then)
+    int ensure(udpdk_gpu_ctx *c)
+    {
+        const int rc = dev.ensure(c, 1);
+        return rc ? rc : host.ensure(c, 1);
+    }
+    int enqueue_fetch(udpdk_gpu_ctx *c, hipStream_t st)
+    {
+        return hip_rc(c, hipMemcpyAsync(host.p, dev.p, sizeof(R), hipMemcpyDeviceToHost, st));
+    }
+    int fetch(udpdk_gpu_ctx *c, hipStream_t st)
+    {
+        const int rc = enqueue_fetch(c, st);
+        return rc ? rc : hip_rc(c, hipStreamSynchronize(st));
+    }
+    void release() { release_all(dev, host); }
 };
 
-// Workspace of the reuse-port balance stage (rx_balance.hip): the filter's compaction workspace,
-// the frames' choices and the count of balanced frames. One per pipe for the sticky mode
-// (udpdk_gpu_rx_balance) and one for explicit udpdk_gpu_rx_balance_select calls.
-struct BalanceWs {
-    FilterWs f;
-    uint32_t *chosen = nullptr; size_t chosen_cap = 0;
-    uint32_t *cnt = nullptr; size_t cnt_cap = 0;          // frames balanced
-    uint32_t *h_cnt = nullptr; size_t h_cnt_cap = 0;      // pinned mirror
+// Workspace of a lane-removal stage (lane_stage: the drop filter, the balance, the peer filter),
+// lazily sized: per stage one per pipe for the sticky mode and one for the explicit calls.
+struct FilterWs {
+    DevBuf<unsigned long long> mask;
+    DevBuf<uint32_t> row, base;
+    DevBuf<uint32_t> pkt, off;                 // sticky mode: the filtered set before it goes back
+                                               // into the caller's buffers
+    ResultSlot<FilterResult> res;
+    hipStream_t stream = nullptr;              // of the last run
+    uint32_t out_cap = 0;
+    void release() { release_all(mask, row, base, pkt, off, res); }
+};
+
+// Workspace of the reuse-port balance stage (rx_balance.hip): the compaction workspace, the
+// frames' choices and the count of balanced frames.
+struct BalanceWs : FilterWs {
+    DevBuf<uint32_t> chosen;
+    DevBuf<uint32_t> cnt;                      // frames balanced
+    PinnedBuf<uint32_t> h_cnt;
+    void release()
+    {
+        FilterWs::release();
+        release_all(chosen, cnt, h_cnt);
+    }
 };
 
 // Workspace of the reply plan (tx_reply.hip), lazily sized; one per context (the context stream).
 struct ReplyWs {
-    uint32_t *row = nullptr; size_t row_cap = 0;
-    unsigned long long *base = nullptr; size_t base_cap = 0;
-    ReplyResult *res = nullptr; size_t res_cap = 0;
-    ReplyResult *h_res = nullptr; size_t h_res_cap = 0;    // pinned mirror
-    bool ran = false;                                 // a plan was enqueued (udpdk_gpu_tx_reply_stats)
+    DevBuf<uint32_t> row;
+    DevBuf<unsigned long long> base;
+    ResultSlot<ReplyResult> res;
+    void release() { release_all(row, base, res); }
 };
 
 // Workspace of the ICMP reply stage (icmp_reply.hip), lazily sized by the context's max_frames: one
 // for the context stream (udpdk_gpu_icmp_reply) and one per pipe (udpdk_gpu_pipe_icmp_reply).
 struct IcmpWs {
-    IcmpEntry *cand = nullptr; size_t cand_cap = 0;
-    uint32_t *row = nullptr; size_t row_cap = 0;       // the rows, then ubase and rbase
-    unsigned long long *bbase = nullptr; size_t bbase_cap = 0;
-    IcmpResult *res = nullptr; size_t res_cap = 0;
-    IcmpResult *h_res = nullptr; size_t h_res_cap = 0;     // pinned mirror
-    bool ran = false;                                 // a stage was enqueued (udpdk_gpu_icmp_stats)
+    DevBuf<IcmpEntry> cand;
+    DevBuf<uint32_t> row;                      // the rows, then ubase and rbase
+    DevBuf<unsigned long long> bbase;
+    ResultSlot<IcmpResult> res;
+    void release() { release_all(cand, row, bbase, res); }
 };
 
-// Workspace of the ICMP error stage (icmp_error.hip): its counters. One for the context stream
+// The ICMP error stage (icmp_error.hip) keeps only its counters: one slot for the context stream
 // (udpdk_gpu_icmp_errors) and one per pipe (udpdk_gpu_pipe_icmp_errors).
-struct IcmpErrWs {
-    IcmpErrResult *res = nullptr; size_t res_cap = 0;
-    IcmpErrResult *h_res = nullptr; size_t h_res_cap = 0;  // pinned mirror
-    bool ran = false;                                 // a stage was enqueued (udpdk_gpu_icmp_err_stats)
-};
+using IcmpErrWs = ResultSlot<IcmpErrResult>;
+
+// The sticky lane-removal stages, in the order rx_on_pipe applies them.
+enum { ST_DROP, ST_BALANCE, ST_PEER, N_STICKY };
 
 // One RX pipe = a stream and the per-call workspace. With pipelining depth d > 1, consecutive
 // udpdk_gpu_rx calls rotate over d pipes, so one batch's prologue, tail and compaction overlap
@@ -111,41 +180,40 @@ struct IcmpErrWs {
 // the box's 4 hardware queues with the context stream's own traffic).
 struct Pipe {
     hipStream_t stream = nullptr;
-    uint32_t *hist = nullptr;
-    uint32_t *partial = nullptr;
-    uint32_t *base = nullptr;                 // [tiles][lanes] absolute positions (rx_scan_cols)
-    unsigned long long *agg = nullptr;        // rx_scan_cols look-back words, one per lane block
-    uint32_t *ticket = nullptr;               // rx_scan_cols lane-block tickets
+    DevBuf<uint32_t> hist, partial;
+    DevBuf<uint32_t> base;                    // [tiles][lanes] absolute positions (rx_scan_cols)
+    DevBuf<unsigned long long> agg;           // rx_scan_cols look-back words, one per lane block
+    DevBuf<uint32_t> ticket;                  // rx_scan_cols lane-block tickets
     uint32_t epoch = 0;                       // rx_scan_cols calls on this pipe (look-back tag)
     uint32_t spec_epoch = 0;                  // speculative compaction calls (DevResult::nonfull tag)
-    unsigned long long *fuse = nullptr;       // rx_classify fused-completion fan-in words (zeroed)
-    uint32_t *tile_cnt = nullptr;
-    DevResult *res = nullptr;                 // counters, total (device)
-    DevResult *h_res = nullptr;               // pinned mirror, filled by udpdk_gpu_rx_stats
+    DevBuf<unsigned long long> fuse;          // rx_classify fused-completion fan-in words (zeroed)
+    DevBuf<uint32_t> tile_cnt;
+    ResultSlot<DevResult> res;                // counters, total; the mirror is filled by enqueue_result
     hipEvent_t tail = nullptr;                // join point for udpdk_gpu_join
     bool dirty = false;                       // work enqueued since the last join
     uint32_t last_tiles = 0;                  // tiles of this pipe's last call (counter rows)
     uint32_t last_lane_cap = 0;
     FilterWs flt;                             // sticky drop filter
-    bool filtered = false;                    // this pipe's last call ran it
     BalanceWs bal;                            // sticky reuse-port balance
-    bool balanced = false;                    // this pipe's last call ran it
-    FilterWs peer;                            // sticky peer filter (rx_peer.hip: the filter's workspace)
-    bool peered = false;                      // this pipe's last call ran it
-    const udpdk_rx_stats_t *stats_of = nullptr;   // the stats block read_result filled last, and what
-    uint32_t n_dropped = 0, n_balanced = 0;       // each stage removed in that call (udpdk_gpu_rx_removed,
-    uint32_t n_refused = 0;                       // udpdk_gpu_rx_peer_removed)
+    FilterWs peer;                            // sticky peer filter
+    FilterWs *const sticky[N_STICKY] = {&flt, &bal, &peer};
+    bool sticky_ran[N_STICKY] = {};           // this pipe's last call ran the stage
+    const udpdk_rx_stats_t *stats_of = nullptr;   // the stats block read_result filled last, and what each
+    uint32_t removed[N_STICKY] = {};              // stage removed in that call (udpdk_gpu_rx_removed,
+                                                  // udpdk_gpu_rx_peer_removed)
     // host-resident batches (udpdk_gpu_rx_host[_async]): staging, lazily sized
-    uint8_t *st_frames_d = nullptr; size_t st_frames_dcap = 0;
-    uint8_t *st_frames_h = nullptr; size_t st_frames_hcap = 0;
-    uint8_t *st_desc_d = nullptr; size_t st_desc_dcap = 0;
-    uint8_t *st_desc_h = nullptr; size_t st_desc_hcap = 0;
-    uint8_t *st_out_d = nullptr; size_t st_out_cap = 0;
+    DevBuf<uint8_t> st_frames_d, st_desc_d, st_out_d;
+    PinnedBuf<uint8_t> st_frames_h, st_desc_h;
     udpdk_rx_stats_t *host_stats = nullptr;   // outstanding async host call: where its stats go
     udpdk_rx_batch_t staged{};                // device view of the last host batch staged here
     const uint32_t *staged_meta = nullptr;    // and its verdict words
     IcmpWs icmp;                              // udpdk_gpu_pipe_icmp_reply on this pipe's stream
     IcmpErrWs icmp_err;                       // udpdk_gpu_pipe_icmp_errors on this pipe's stream
+    void release()
+    {
+        release_all(hist, partial, base, agg, ticket, fuse, tile_cnt, res, flt, bal, peer, st_frames_d,
+                    st_desc_d, st_out_d, st_frames_h, st_desc_h, icmp, icmp_err);
+    }
 };
 constexpr int MAX_PIPES = 4;
 constexpr size_t FUSE_BYTES = 128u * UDPDK_FUSE_LINES;   // one 128-B line per fan-in / repair word
@@ -165,11 +233,10 @@ struct udpdk_gpu_ctx {
     uint32_t max_frames = 0, max_lanes = 0;
 
     // bind snapshot (device)
-    uint4 *port_tab = nullptr;          // [65536]
-    uint2 *binds = nullptr;
-    uint32_t binds_cap = 0;
-    uint4 *slots = nullptr;
-    uint32_t slots_cap = 0, n_slots = 0;
+    DevBuf<uint4> port_tab;             // [65536]
+    DevBuf<uint2> binds;
+    DevBuf<uint4> slots;
+    uint32_t n_slots = 0;
     uint32_t n_lanes = 1, lane_mask = 0xFFFFFFFFu, key_bits = 0, max_fanout = 0;
     // the bound ports when there are at most UDPDK_INLINE_PORTS (RxArgs::inl)
     uint32_t inl = 0, n_inl = 0, inl_port[UDPDK_INLINE_PORTS] = {};
@@ -179,7 +246,7 @@ struct udpdk_gpu_ctx {
     // of the last call that ran a tail pass / had a tile before the last not full. The single-lane
     // path takes rx_classify<1> and the fused completion while neither was seen in the last
     // UDPDK_HINT_WINDOW calls; both forms are exact for any batch, the hint only picks the faster.
-    uint32_t *hint = nullptr;
+    PinnedBuf<uint32_t> hint;
     uint32_t rx_seq = 0;
     bool have_snapshot = false;
 
@@ -196,13 +263,13 @@ struct udpdk_gpu_ctx {
     FilterWs xflt;                            // explicit udpdk_gpu_rx_filter calls
     FilterWs *flt_last = nullptr;             // the last filter run (udpdk_gpu_rx_drop_stats)
     bool bal_on = false;                      // udpdk_gpu_rx_balance: the sticky balance stage
-    uint8_t *bal_rp = nullptr;                // [max_lanes] its lane flags (zero past what was given)
-    uint32_t *bal_ktab = nullptr;             // key windows of the default RSS configuration (no
+    DevBuf<uint8_t> bal_rp;                   // [max_lanes] its lane flags (zero past what was given)
+    DevBuf<uint32_t> bal_ktab;                // key windows of the default RSS configuration (no
                                               // udpdk_gpu_rss_config on this context)
     BalanceWs xbal;                           // explicit udpdk_gpu_rx_balance_select calls
     BalanceWs *bal_last = nullptr;            // the last balance run (udpdk_gpu_rx_balance_stats)
     bool peer_on = false;                     // udpdk_gpu_rx_peer: the sticky peer filter
-    uint2 *peer_tab = nullptr;                // [max_lanes] its records (off past what was given)
+    DevBuf<uint2> peer_tab;                   // [max_lanes] its records (off past what was given)
     FilterWs xpeer;                           // explicit udpdk_gpu_rx_peer_select calls
     FilterWs *peer_last = nullptr;            // the last peer filter run (udpdk_gpu_rx_peer_stats)
     ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
@@ -214,11 +281,11 @@ struct udpdk_gpu_ctx {
     // receive-side scaling (udpdk_gpu_rss_config)
     bool rss_ready = false;
     RssArgs rss{};
-    uint16_t *rss_reta = nullptr;
-    uint32_t *rss_ktab = nullptr;             // [12][256] key windows
-    uint8_t *rss_qid = nullptr;
-    uint32_t *rss_hist = nullptr, *rss_partial = nullptr, *rss_total = nullptr;
-    unsigned long long *rss_fuse = nullptr;   // rss_hash fan-in words (fused queue bases)
+    DevBuf<uint16_t> rss_reta;
+    DevBuf<uint32_t> rss_ktab;                // [12][256] key windows
+    DevBuf<uint8_t> rss_qid;
+    DevBuf<uint32_t> rss_hist, rss_partial, rss_total;
+    DevBuf<unsigned long long> rss_fuse;      // rss_hash fan-in words (fused queue bases)
     bool rss_no_fuse = false;                 // UDPDK_RSS_FUSE=0 (tests, A/B): the rss_base launch
     bool rss_trace = false;                   // UDPDK_RSS_TRACE (diagnostic): the form of every call on stderr
 
@@ -229,6 +296,14 @@ struct udpdk_gpu_ctx {
     int n_sets_used = 0;
     double ms[UDPDK_N_KERNEL_IDS] = {};
     uint32_t launches[UDPDK_N_KERNEL_IDS] = {};
+
+    // All the memory above (udpdk_gpu_ctx_destroy; whatever is missing here goes with the context)
+    void release()
+    {
+        for (Pipe &P : pipes) P.release();
+        release_all(port_tab, binds, slots, hint, xflt, bal_rp, bal_ktab, xbal, peer_tab, xpeer, rpl, icmp,
+                    icmp_err, rss_reta, rss_ktab, rss_qid, rss_hist, rss_partial, rss_total, rss_fuse);
+    }
 };
 
 #define HIPC(ctx, expr)                                                      \
@@ -345,26 +420,99 @@ int sync_all(udpdk_gpu_ctx *c)
     return 0;
 }
 
-int ensure_dev(udpdk_gpu_ctx *c, void **p, size_t *cap, size_t need)
+int hip_rc(udpdk_gpu_ctx *c, hipError_t e)
 {
-    if (*cap >= need) return 0;
-    if (*p) HIPC(c, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    HIPC(c, hipMalloc(p, need));
-    *cap = need;
+    HIPC(c, e);
     return 0;
 }
 
-int ensure_host(udpdk_gpu_ctx *c, void **p, size_t *cap, size_t need)
+// How a call that works on the context stream starts, once its arguments have passed: select the
+// device and, with pipelining on, order the other pipes' work before it.
+int on_ctx_stream(udpdk_gpu_ctx *c)
 {
-    if (*cap >= need) return 0;
-    if (*p) HIPC(c, hipHostFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    HIPC(c, hipHostMalloc(p, need, hipHostMallocDefault));
-    *cap = need;
+    HIPC(c, hipSetDevice(c->device));
+    return c->depth > 1 ? join_pipes(c) : 0;
+}
+
+// One lane-removal stage over a lane set on stream st: the stage's mark kernel fills the keep masks
+// and rows, then rx_filter_base and rx_filter_write compact (rx_filter.h). `mark` gets the filled
+// FilterArgs, may adjust them, and enqueues whatever the stage runs before the compaction, ending
+// with launch_mark of its kernel.
+template <typename Mark>
+int lane_stage(udpdk_gpu_ctx *c, FilterWs &W, hipStream_t st, const udpdk_rx_lanes_t *in, uint32_t *off_out,
+               uint32_t *pkt_out, uint32_t out_cap, Mark mark)
+{
+    const uint32_t tiles = ceil_div(in->lane_cap, FLT_TILE);
+    int rc;
+    if ((rc = W.mask.ensure(c, (size_t)tiles * FLT_CHUNKS + 1)) || (rc = W.row.ensure(c, (size_t)tiles * FLT_ROW + 1)) ||
+        (rc = W.base.ensure(c, (size_t)tiles + 1)) || (rc = W.res.ensure(c)))
+        return rc;
+    FilterArgs fa;
+    fa.meta = in->meta_dev;
+    fa.lane_off = in->lane_off_dev;
+    fa.lane_pkt = in->lane_pkt_dev;
+    fa.lane_off_out = off_out;
+    fa.lane_pkt_out = pkt_out;
+    fa.mask = W.mask;
+    fa.row = W.row;
+    fa.base = W.base;
+    fa.res = W.res.dev;
+    fa.n = in->n;
+    fa.lane_cap = in->lane_cap;
+    fa.n_lanes = in->n_lanes;
+    fa.flags = 0;
+    fa.out_cap = out_cap;
+    fa.n_tiles = tiles;
+    if ((rc = mark(fa))) return rc;
+    hipLaunchKernelGGL(rx_filter_base, dim3(1), dim3(FLT_BASE_BLOCK), 0, st, fa);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(rx_filter_write, dim3(tiles + ceil_div(in->n_lanes + 1u, (uint32_t)FLT_BLOCK)),
+                       dim3(FLT_BLOCK), 0, st, fa);
+    HIPC(c, hipGetLastError());
+    W.stream = st;
+    W.out_cap = out_cap;
     return 0;
+}
+
+// A stage's mark kernel, one workgroup per tile of `f` (the FilterArgs inside `args`); no launch
+// for an empty grid.
+template <typename K, typename A>
+int launch_mark(udpdk_gpu_ctx *c, hipStream_t st, K kern, const A &args, const FilterArgs &f)
+{
+    if (!f.n_tiles) return 0;
+    hipLaunchKernelGGL(kern, dim3(f.n_tiles), dim3(FLT_BLOCK), 0, st, args);
+    HIPC(c, hipGetLastError());
+    return 0;
+}
+
+// One sticky stage of rx_on_pipe, on the pipe's stream: `enqueue` runs the stage from the caller's
+// buffers into the workspace's off / pkt, and rx_filter_copy puts what it kept back into the
+// caller's buffers.
+template <typename Enqueue>
+int sticky_stage(udpdk_gpu_ctx *c, Pipe &P, int stage, const udpdk_rx_out_t *o, Enqueue enqueue)
+{
+    FilterWs &W = *P.sticky[stage];
+    const uint32_t S = c->n_lanes;
+    const uint32_t tiles = ceil_div(o->lane_cap, FLT_TILE);
+    int rc;
+    if ((rc = W.pkt.ensure(c, (size_t)o->lane_cap + 1)) || (rc = W.off.ensure(c, (size_t)S + 1)) ||
+        (rc = enqueue(W.off.p, W.pkt.p)))
+        return rc;
+    hipLaunchKernelGGL(rx_filter_copy, dim3(tiles + ceil_div(S + 1u, (uint32_t)FLT_BLOCK)), dim3(FLT_BLOCK), 0,
+                       P.stream, (const uint32_t *)W.off, (const uint32_t *)W.pkt, (const FilterResult *)W.res.dev,
+                       o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
+    HIPC(c, hipGetLastError());
+    P.sticky_ran[stage] = true;
+    return 0;
+}
+
+// The context-stream form of a *_stats call: the stage's result into its mirror, waited for.
+template <typename R>
+int ctx_result(udpdk_gpu_ctx *c, ResultSlot<R> &slot)
+{
+    if (!slot.ran) return -ENOENT;
+    HIPC(c, hipSetDevice(c->device));
+    return slot.fetch(c, c->stream);
 }
 
 } // namespace
@@ -412,27 +560,27 @@ int udpdk_gpu_ctx_create(int device, uint32_t max_frames, uint32_t max_lanes, ud
         }
         if (!ok) break;
         c->stream = c->pipes[0].stream;
-        if (hipMalloc((void **)&c->port_tab, UDPDK_UDP_PORTS * sizeof(uint4)) != hipSuccess) break;
+        if (c->port_tab.ensure(c, UDPDK_UDP_PORTS)) break;
         if (hipMemset(c->port_tab, 0, UDPDK_UDP_PORTS * sizeof(uint4)) != hipSuccess) break;
         for (Pipe &P : c->pipes) {
-            ok = ok && hipMalloc((void **)&P.hist, c->caps.hist_cap * 4) == hipSuccess;
-            ok = ok && hipMalloc((void **)&P.partial, c->caps.partial_cap * 4) == hipSuccess;
-            ok = ok && hipMalloc((void **)&P.base, c->caps.hist_cap * 4) == hipSuccess;
+            ok = ok && !P.hist.ensure(c, c->caps.hist_cap);
+            ok = ok && !P.partial.ensure(c, c->caps.partial_cap);
+            ok = ok && !P.base.ensure(c, c->caps.hist_cap);
             // one look-back word per lane block: down to one lane per block when a batch has so
             // many tiles that a column chunk holds a single lane (rx_scan_cols' lb = 0)
-            ok = ok && hipMalloc((void **)&P.agg, ((size_t)max_lanes + 1) * 8) == hipSuccess;
+            ok = ok && !P.agg.ensure(c, (size_t)max_lanes + 1);
             ok = ok && hipMemset(P.agg, 0, ((size_t)max_lanes + 1) * 8) == hipSuccess;
-            ok = ok && hipMalloc((void **)&P.ticket, 64) == hipSuccess;
+            ok = ok && !P.ticket.ensure(c, 64 / 4);
             ok = ok && hipMemset(P.ticket, 0, 64) == hipSuccess;
-            ok = ok && hipMalloc((void **)&P.tile_cnt, c->caps.tiles_cap * UDPDK_N_COUNTERS * 4) == hipSuccess;
-            ok = ok && hipMalloc((void **)&P.res, sizeof(DevResult)) == hipSuccess;
-            ok = ok && hipMemset(P.res, 0, sizeof(DevResult)) == hipSuccess;
-            ok = ok && hipHostMalloc((void **)&P.h_res, sizeof(DevResult), hipHostMallocDefault) == hipSuccess;
-            ok = ok && hipMalloc((void **)&P.fuse, FUSE_BYTES) == hipSuccess;
+            ok = ok && !P.tile_cnt.ensure(c, (size_t)c->caps.tiles_cap * UDPDK_N_COUNTERS);
+            ok = ok && !P.res.dev.ensure(c, 1);
+            ok = ok && hipMemset(P.res.dev, 0, sizeof(DevResult)) == hipSuccess;
+            ok = ok && !P.res.host.ensure(c, 1);
+            ok = ok && !P.fuse.ensure(c, FUSE_BYTES / 8);
             ok = ok && hipMemset(P.fuse, 0, FUSE_BYTES) == hipSuccess;
         }
         // fine-grained (coherent) host memory: the kernels' hint stores go straight to it
-        ok = ok && hipHostMalloc((void **)&c->hint, HINT_BYTES, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
+        ok = ok && !c->hint.ensure(c, HINT_BYTES / 4, hipHostMallocCoherent | hipHostMallocMapped);
         if (ok) {
             // a fresh context starts on the two-launch form (as if call 1 had a tile not full):
             // the fused completion's rewrite of a not-full call is one workgroup's work
@@ -480,66 +628,14 @@ int udpdk_gpu_ctx_destroy(udpdk_gpu_ctx *c)
         if (P.stream) (void)hipStreamSynchronize(P.stream);
     reasm_destroy(c->reasm);
     c->reasm = nullptr;
-    for (void *p : {(void *)c->rss_reta, (void *)c->rss_ktab, (void *)c->rss_qid, (void *)c->rss_hist,
-                    (void *)c->rss_partial, (void *)c->rss_total, (void *)c->rss_fuse})
-        if (p) (void)hipFree(p);
-    void *dev[] = {c->port_tab, c->binds, c->slots};
-    for (void *p : dev) if (p) (void)hipFree(p);
-    FilterWs *fw[MAX_PIPES + 1] = {&c->xflt};
-    for (int i = 0; i < MAX_PIPES; ++i) fw[i + 1] = &c->pipes[i].flt;
-    for (FilterWs *W : fw) {
-        void *pd[] = {W->mask, W->row, W->base, W->pkt, W->off, W->res};
-        for (void *p : pd) if (p) (void)hipFree(p);
-        if (W->h_res) (void)hipHostFree(W->h_res);
-    }
-    BalanceWs *bw[MAX_PIPES + 1] = {&c->xbal};
-    for (int i = 0; i < MAX_PIPES; ++i) bw[i + 1] = &c->pipes[i].bal;
-    for (BalanceWs *W : bw) {
-        void *pd[] = {W->f.mask, W->f.row, W->f.base, W->f.pkt, W->f.off, W->f.res, W->chosen, W->cnt};
-        for (void *p : pd) if (p) (void)hipFree(p);
-        if (W->f.h_res) (void)hipHostFree(W->f.h_res);
-        if (W->h_cnt) (void)hipHostFree(W->h_cnt);
-    }
-    for (void *p : {(void *)c->bal_rp, (void *)c->bal_ktab, (void *)c->peer_tab})
-        if (p) (void)hipFree(p);
-    FilterWs *pw[MAX_PIPES + 1] = {&c->xpeer};
-    for (int i = 0; i < MAX_PIPES; ++i) pw[i + 1] = &c->pipes[i].peer;
-    for (FilterWs *W : pw) {
-        void *pd[] = {W->mask, W->row, W->base, W->pkt, W->off, W->res};
-        for (void *p : pd) if (p) (void)hipFree(p);
-        if (W->h_res) (void)hipHostFree(W->h_res);
-    }
-    for (void *p : {(void *)c->rpl.row, (void *)c->rpl.base, (void *)c->rpl.res})
-        if (p) (void)hipFree(p);
-    if (c->rpl.h_res) (void)hipHostFree(c->rpl.h_res);
-    IcmpWs *iw[MAX_PIPES + 1] = {&c->icmp};
-    for (int i = 0; i < MAX_PIPES; ++i) iw[i + 1] = &c->pipes[i].icmp;
-    for (IcmpWs *W : iw) {
-        void *pd[] = {W->cand, W->row, W->bbase, W->res};
-        for (void *p : pd) if (p) (void)hipFree(p);
-        if (W->h_res) (void)hipHostFree(W->h_res);
-    }
-    IcmpErrWs *ew[MAX_PIPES + 1] = {&c->icmp_err};
-    for (int i = 0; i < MAX_PIPES; ++i) ew[i + 1] = &c->pipes[i].icmp_err;
-    for (IcmpErrWs *W : ew) {
-        if (W->res) (void)hipFree(W->res);
-        if (W->h_res) (void)hipHostFree(W->h_res);
-    }
-    for (Pipe &P : c->pipes) {
-        void *ph[] = {P.st_frames_h, P.st_desc_h};
-        for (void *p : ph) if (p) (void)hipHostFree(p);
-        void *pd[] = {P.hist, P.partial, P.base, P.agg, P.ticket, P.tile_cnt, P.res, P.st_frames_d,
-                      P.st_desc_d, P.st_out_d, P.fuse};
-        for (void *p : pd) if (p) (void)hipFree(p);
-        if (P.h_res) (void)hipHostFree(P.h_res);
+    c->release();
+    for (Pipe &P : c->pipes)
         if (P.tail) (void)hipEventDestroy(P.tail);
-    }
     if (c->sets) {
         for (int i = 0; i < EVENT_SETS; ++i)
             for (int k = 0; k < 2 * TIMED_KERNELS; ++k) (void)hipEventDestroy(c->sets[i].ev[k]);
         delete[] c->sets;
     }
-    if (c->hint) (void)hipHostFree(c->hint);
     for (Pipe &P : c->pipes)
         if (P.stream) (void)hipStreamDestroy(P.stream);
     delete c;
@@ -662,27 +758,12 @@ int udpdk_gpu_bind_snapshot_upload(udpdk_gpu_ctx *c, const udpdk_bind_snapshot_t
     }
     HIPC(c, hipSetDevice(c->device));
     { int rc = sync_all(c); if (rc) return rc; }
-    if (s->n_binds > c->binds_cap) {
-        if (c->binds) HIPC(c, hipFree(c->binds));
-        c->binds = nullptr;
-        c->binds_cap = 0;
-        HIPC(c, hipMalloc((void **)&c->binds, (size_t)s->n_binds * sizeof(uint2)));
-        c->binds_cap = s->n_binds;
-    }
-    if (!c->binds) {
-        HIPC(c, hipMalloc((void **)&c->binds, sizeof(uint2)));
-        c->binds_cap = 1;
-    }
+    { int rc = c->binds.ensure(c, std::max<uint32_t>(s->n_binds, 1u)); if (rc) return rc; }   // (never null)
     HIPC(c, hipMemcpy(c->port_tab, tab.data(), UDPDK_UDP_PORTS * sizeof(uint4), hipMemcpyHostToDevice));
     if (s->n_binds)
         HIPC(c, hipMemcpy(c->binds, b.data(), (size_t)s->n_binds * sizeof(uint2), hipMemcpyHostToDevice));
     if (s->n_slots) {
-        if (s->n_slots > c->slots_cap) {
-            if (c->slots) HIPC(c, hipFree(c->slots));
-            c->slots = nullptr;
-            HIPC(c, hipMalloc((void **)&c->slots, (size_t)s->n_slots * sizeof(uint4)));
-            c->slots_cap = s->n_slots;
-        }
+        { int rc = c->slots.ensure(c, s->n_slots); if (rc) return rc; }
         std::vector<uint4> sl(s->n_slots);
         for (uint32_t i = 0; i < s->n_slots; ++i)
             sl[i] = make_uint4(s->slots[i].ip, s->slots[i].udp_port & 0xFFFFu, s->slots[i].bound ? 1u : 0u, 0u);
@@ -736,47 +817,16 @@ int udpdk_gpu_timing_read(udpdk_gpu_ctx *c, double ms[UDPDK_N_KERNEL_IDS],
 
 namespace {
 
-// The lane filter (rx_filter.hip) over one lane set on stream st: mark, base, write.
+// The drop filter (rx_filter.hip): entries out by verdict-word flags.
 int filter_enqueue(udpdk_gpu_ctx *c, FilterWs &W, hipStream_t st, const udpdk_rx_lanes_t *in, uint32_t flags,
                    uint32_t *off_out, uint32_t *pkt_out, uint32_t out_cap)
 {
-    const uint32_t tiles = ceil_div(in->lane_cap, FLT_TILE);
-    int rc;
-    if ((rc = ensure_dev(c, (void **)&W.mask, &W.mask_cap, ((size_t)tiles * FLT_CHUNKS + 1) * 8)) ||
-        (rc = ensure_dev(c, (void **)&W.row, &W.row_cap, ((size_t)tiles * FLT_ROW + 1) * 4)) ||
-        (rc = ensure_dev(c, (void **)&W.base, &W.base_cap, ((size_t)tiles + 1) * 4)) ||
-        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(FilterResult))) ||
-        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(FilterResult))))
-        return rc;
-    FilterArgs fa;
-    fa.meta = in->meta_dev;
-    fa.lane_off = in->lane_off_dev;
-    fa.lane_pkt = in->lane_pkt_dev;
-    fa.lane_off_out = off_out;
-    fa.lane_pkt_out = pkt_out;
-    fa.mask = W.mask;
-    fa.row = W.row;
-    fa.base = W.base;
-    fa.res = W.res;
-    fa.n = in->n;
-    fa.lane_cap = in->lane_cap;
-    fa.n_lanes = in->n_lanes;
-    fa.flags = flags;
-    fa.out_cap = out_cap;
-    fa.n_tiles = tiles;
-    if (tiles) {
-        hipLaunchKernelGGL(rx_filter_mark, dim3(tiles), dim3(FLT_BLOCK), 0, st, fa);
-        HIPC(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(rx_filter_base, dim3(1), dim3(FLT_BASE_BLOCK), 0, st, fa);
-    HIPC(c, hipGetLastError());
-    hipLaunchKernelGGL(rx_filter_write, dim3(tiles + ceil_div(in->n_lanes + 1u, (uint32_t)FLT_BLOCK)),
-                       dim3(FLT_BLOCK), 0, st, fa);
-    HIPC(c, hipGetLastError());
-    W.stream = st;
-    W.out_cap = out_cap;
-    c->flt_last = &W;
-    return 0;
+    const int rc = lane_stage(c, W, st, in, off_out, pkt_out, out_cap, [&](FilterArgs &fa) {
+        fa.flags = flags;
+        return launch_mark(c, st, rx_filter_mark, fa, fa);
+    });
+    if (!rc) c->flt_last = &W;
+    return rc;
 }
 
 // The key-window table the balance stage hashes with: the context's RSS configuration, or the
@@ -793,206 +843,115 @@ int balance_ktab(udpdk_gpu_ctx *c, const uint32_t **ktab, uint32_t *types)
         udpdk_gpu_rss_default_conf(&conf, 1);
         std::vector<uint32_t> tab(12 * 256);
         rss_key_table(conf.key, reinterpret_cast<uint32_t(*)[256]>(tab.data()));
-        uint32_t *d = nullptr;
-        HIPC(c, hipMalloc((void **)&d, tab.size() * sizeof(uint32_t)));
-        if (hipMemcpy(d, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
+        const int rc = c->bal_ktab.ensure(c, tab.size());
+        if (rc) return rc;
+        if (hipMemcpy(c->bal_ktab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            c->bal_ktab.release();
             return -EIO;
         }
-        c->bal_ktab = d;
     }
     *ktab = c->bal_ktab;
     *types = UDPDK_RSS_IPV4 | UDPDK_RSS_NONFRAG_IPV4_UDP;
     return 0;
 }
 
-// The balance stage (rx_balance.hip) over one lane set on stream st: pick, mark, then the filter's
-// base and write.
+// The balance stage (rx_balance.hip): every frame's choice among its reuse-port lanes by flow hash
+// (pick), then the entries in lanes not chosen out.
 int balance_enqueue(udpdk_gpu_ctx *c, BalanceWs &B, hipStream_t st, const udpdk_rx_batch_t *bt,
                     const udpdk_rx_lanes_t *in, const uint8_t *lane_rp, const uint32_t *hash_dev,
                     uint32_t *off_out, uint32_t *pkt_out, uint32_t out_cap)
 {
-    FilterWs &W = B.f;
-    const uint32_t tiles = ceil_div(in->lane_cap, FLT_TILE);
     const uint32_t *ktab = nullptr;
     uint32_t types = 0;
-    int rc;
-    if ((rc = balance_ktab(c, &ktab, &types)) ||
-        (rc = ensure_dev(c, (void **)&W.mask, &W.mask_cap, ((size_t)tiles * FLT_CHUNKS + 1) * 8)) ||
-        (rc = ensure_dev(c, (void **)&W.row, &W.row_cap, ((size_t)tiles * FLT_ROW + 1) * 4)) ||
-        (rc = ensure_dev(c, (void **)&W.base, &W.base_cap, ((size_t)tiles + 1) * 4)) ||
-        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(FilterResult))) ||
-        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(FilterResult))) ||
-        (rc = ensure_dev(c, (void **)&B.chosen, &B.chosen_cap, ((size_t)in->n + 1) * 4)) ||
-        (rc = ensure_dev(c, (void **)&B.cnt, &B.cnt_cap, 4)) ||
-        (rc = ensure_host(c, (void **)&B.h_cnt, &B.h_cnt_cap, 4)))
-        return rc;
-    HIPC(c, hipMemsetAsync(B.cnt, 0, 4, st));
-    if (in->n) {
-        BalancePickArgs pa;
-        pa.frames = bt->frames_dev;
-        pa.offset = bt->offset_dev;
-        pa.meta = in->meta_dev;
-        pa.port_tab = c->port_tab;
-        pa.binds = c->binds;
-        pa.lane_rp = lane_rp;
-        pa.hash_in = hash_dev;
-        pa.ktab = ktab;
-        pa.chosen = B.chosen;
-        pa.balanced = B.cnt;
-        pa.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
-        pa.n = in->n;
-        pa.n_lanes = in->n_lanes;
-        pa.hash_types = types;
-        hipLaunchKernelGGL(rx_balance_pick, dim3(ceil_div(in->n, BAL_TILE)), dim3(BAL_BLOCK), 0, st, pa);
-        HIPC(c, hipGetLastError());
-    }
-    BalanceMarkArgs ma;
-    FilterArgs &fa = ma.f;
-    fa.meta = in->meta_dev;
-    fa.lane_off = in->lane_off_dev;
-    fa.lane_pkt = in->lane_pkt_dev;
-    fa.lane_off_out = off_out;
-    fa.lane_pkt_out = pkt_out;
-    fa.mask = W.mask;
-    fa.row = W.row;
-    fa.base = W.base;
-    fa.res = W.res;
-    fa.n = in->n;
-    fa.lane_cap = in->lane_cap;
-    fa.n_lanes = in->n_lanes;
-    fa.flags = 0;
-    fa.out_cap = out_cap;
-    fa.n_tiles = tiles;
-    ma.chosen = B.chosen;
-    ma.lane_rp = lane_rp;
-    if (tiles) {
-        hipLaunchKernelGGL(rx_balance_mark, dim3(tiles), dim3(FLT_BLOCK), 0, st, ma);
-        HIPC(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(rx_filter_base, dim3(1), dim3(FLT_BASE_BLOCK), 0, st, fa);
-    HIPC(c, hipGetLastError());
-    hipLaunchKernelGGL(rx_filter_write, dim3(tiles + ceil_div(in->n_lanes + 1u, (uint32_t)FLT_BLOCK)),
-                       dim3(FLT_BLOCK), 0, st, fa);
-    HIPC(c, hipGetLastError());
-    W.stream = st;
-    W.out_cap = out_cap;
-    c->bal_last = &B;
-    return 0;
+    int rc = balance_ktab(c, &ktab, &types);
+    if (rc) return rc;
+    rc = lane_stage(c, B, st, in, off_out, pkt_out, out_cap, [&](FilterArgs &fa) {
+        int rc;
+        if ((rc = B.chosen.ensure(c, (size_t)in->n + 1)) || (rc = B.cnt.ensure(c, 1)) || (rc = B.h_cnt.ensure(c, 1)))
+            return rc;
+        HIPC(c, hipMemsetAsync(B.cnt, 0, 4, st));
+        if (in->n) {
+            BalancePickArgs pa;
+            pa.frames = bt->frames_dev;
+            pa.offset = bt->offset_dev;
+            pa.meta = in->meta_dev;
+            pa.port_tab = c->port_tab;
+            pa.binds = c->binds;
+            pa.lane_rp = lane_rp;
+            pa.hash_in = hash_dev;
+            pa.ktab = ktab;
+            pa.chosen = B.chosen;
+            pa.balanced = B.cnt;
+            pa.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+            pa.n = in->n;
+            pa.n_lanes = in->n_lanes;
+            pa.hash_types = types;
+            hipLaunchKernelGGL(rx_balance_pick, dim3(ceil_div(in->n, BAL_TILE)), dim3(BAL_BLOCK), 0, st, pa);
+            HIPC(c, hipGetLastError());
+        }
+        BalanceMarkArgs ma;
+        ma.f = fa;
+        ma.chosen = B.chosen;
+        ma.lane_rp = lane_rp;
+        return launch_mark(c, st, rx_balance_mark, ma, fa);
+    });
+    if (!rc) c->bal_last = &B;
+    return rc;
 }
 
-// The peer filter (rx_peer.hip) over one lane set on stream st: mark, then the filter's base and
-// write.
+// The peer filter (rx_peer.hip): a connected lane's entries from anyone but its peer out.
 int peer_enqueue(udpdk_gpu_ctx *c, FilterWs &W, hipStream_t st, const udpdk_rx_batch_t *bt,
                  const udpdk_rx_lanes_t *in, const uint2 *peer, uint32_t *off_out, uint32_t *pkt_out,
                  uint32_t out_cap)
 {
-    const uint32_t tiles = ceil_div(in->lane_cap, FLT_TILE);
-    int rc;
-    if ((rc = ensure_dev(c, (void **)&W.mask, &W.mask_cap, ((size_t)tiles * FLT_CHUNKS + 1) * 8)) ||
-        (rc = ensure_dev(c, (void **)&W.row, &W.row_cap, ((size_t)tiles * FLT_ROW + 1) * 4)) ||
-        (rc = ensure_dev(c, (void **)&W.base, &W.base_cap, ((size_t)tiles + 1) * 4)) ||
-        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(FilterResult))) ||
-        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(FilterResult))))
-        return rc;
-    PeerMarkArgs ma;
-    FilterArgs &fa = ma.f;
-    fa.meta = nullptr;
-    fa.lane_off = in->lane_off_dev;
-    fa.lane_pkt = in->lane_pkt_dev;
-    fa.lane_off_out = off_out;
-    fa.lane_pkt_out = pkt_out;
-    fa.mask = W.mask;
-    fa.row = W.row;
-    fa.base = W.base;
-    fa.res = W.res;
-    fa.n = in->n;
-    fa.lane_cap = in->lane_cap;
-    fa.n_lanes = in->n_lanes;
-    fa.flags = 0;
-    fa.out_cap = out_cap;
-    fa.n_tiles = tiles;
-    ma.peer = peer;
-    ma.frames = bt->frames_dev;
-    ma.offset = bt->offset_dev;
-    ma.length = bt->length_dev;
-    ma.frames_bytes = (uint32_t)bt->frames_bytes;
-    ma.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
-    if (tiles) {
-        hipLaunchKernelGGL(rx_peer_mark, dim3(tiles), dim3(FLT_BLOCK), 0, st, ma);
-        HIPC(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(rx_filter_base, dim3(1), dim3(FLT_BASE_BLOCK), 0, st, fa);
-    HIPC(c, hipGetLastError());
-    hipLaunchKernelGGL(rx_filter_write, dim3(tiles + ceil_div(in->n_lanes + 1u, (uint32_t)FLT_BLOCK)),
-                       dim3(FLT_BLOCK), 0, st, fa);
-    HIPC(c, hipGetLastError());
-    W.stream = st;
-    W.out_cap = out_cap;
-    c->peer_last = &W;
-    return 0;
+    const int rc = lane_stage(c, W, st, in, off_out, pkt_out, out_cap, [&](FilterArgs &fa) {
+        fa.meta = nullptr;
+        PeerMarkArgs ma;
+        ma.f = fa;
+        ma.peer = peer;
+        ma.frames = bt->frames_dev;
+        ma.offset = bt->offset_dev;
+        ma.length = bt->length_dev;
+        ma.frames_bytes = (uint32_t)bt->frames_bytes;
+        ma.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+        return launch_mark(c, st, rx_peer_mark, ma, fa);
+    });
+    if (!rc) c->peer_last = &W;
+    return rc;
 }
 
 int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udpdk_rx_out_t *o);
 
 // One batch's RX on a pipe: the launch sequence that makes the lanes (whichever form it takes),
-// then, in sticky drop mode, the filter from the caller's buffers into the pipe's workspace and
-// the filtered set back into the caller's buffers, all on the pipe's stream.
+// then the sticky stages that are on (sticky_stage), each on what the one before left, all on the
+// pipe's stream. They are per-entry predicates that do not depend on what else the lanes hold, so
+// they commute: one removes every entry of a frame, one picks by a hash that does not depend on
+// the lanes, one looks at the entry's own lane and frame.
 int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udpdk_rx_out_t *o)
 {
     int rc = rx_lanes_on_pipe(c, pipe, bt, o);
     if (rc) return rc;
     Pipe &P = c->pipes[pipe];
-    P.filtered = false;
-    P.balanced = false;
-    P.peered = false;
+    for (bool &ran : P.sticky_ran) ran = false;
     if ((!c->drop_flags && !c->bal_on && !c->peer_on) || bt->n == 0) return 0;   // (no frames: the lanes are empty)
-    const uint32_t S = c->n_lanes;
-    const udpdk_rx_lanes_t in = {o->meta_dev, bt->n, o->lane_off_dev, o->lane_pkt_dev, o->lane_cap, S};
-    const uint32_t tiles = ceil_div(o->lane_cap, FLT_TILE);
-    if (c->drop_flags) {
-        FilterWs &W = P.flt;
-        if ((rc = ensure_dev(c, (void **)&W.pkt, &W.pkt_cap, ((size_t)o->lane_cap + 1) * 4)) ||
-            (rc = ensure_dev(c, (void **)&W.off, &W.off_cap, ((size_t)S + 1) * 4)))
-            return rc;
-        if ((rc = filter_enqueue(c, W, P.stream, &in, c->drop_flags, W.off, W.pkt, o->lane_cap))) return rc;
-        hipLaunchKernelGGL(rx_filter_copy, dim3(tiles + ceil_div(S + 1u, (uint32_t)FLT_BLOCK)), dim3(FLT_BLOCK), 0,
-                           P.stream, (const uint32_t *)W.off, (const uint32_t *)W.pkt, (const FilterResult *)W.res,
-                           o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
-        HIPC(c, hipGetLastError());
-        P.filtered = true;
-    }
-    if (c->bal_on) {
-        // after the drop filter, on what it left (the two commute: one removes every entry of a
-        // frame, the other picks by a hash that does not depend on the lanes)
-        if (c->lane_mask != 0xFFFFFFFFu) return -EINVAL;       // compat mode: a lane is not a sockfd
-        FilterWs &W = P.bal.f;
-        if ((rc = ensure_dev(c, (void **)&W.pkt, &W.pkt_cap, ((size_t)o->lane_cap + 1) * 4)) ||
-            (rc = ensure_dev(c, (void **)&W.off, &W.off_cap, ((size_t)S + 1) * 4)))
-            return rc;
-        if ((rc = balance_enqueue(c, P.bal, P.stream, bt, &in, c->bal_rp, nullptr, W.off, W.pkt, o->lane_cap)))
-            return rc;
-        hipLaunchKernelGGL(rx_filter_copy, dim3(tiles + ceil_div(S + 1u, (uint32_t)FLT_BLOCK)), dim3(FLT_BLOCK), 0,
-                           P.stream, (const uint32_t *)W.off, (const uint32_t *)W.pkt, (const FilterResult *)W.res,
-                           o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
-        HIPC(c, hipGetLastError());
-        P.balanced = true;
-    }
-    if (c->peer_on) {
-        // after the other two, on what they left (all three are per-entry predicates that do not
-        // depend on what else the lanes hold, so they commute)
-        if (c->lane_mask != 0xFFFFFFFFu) return -EINVAL;       // compat mode: a lane is not a sockfd
-        FilterWs &W = P.peer;
-        if ((rc = ensure_dev(c, (void **)&W.pkt, &W.pkt_cap, ((size_t)o->lane_cap + 1) * 4)) ||
-            (rc = ensure_dev(c, (void **)&W.off, &W.off_cap, ((size_t)S + 1) * 4)))
-            return rc;
-        if ((rc = peer_enqueue(c, W, P.stream, bt, &in, c->peer_tab, W.off, W.pkt, o->lane_cap))) return rc;
-        hipLaunchKernelGGL(rx_filter_copy, dim3(tiles + ceil_div(S + 1u, (uint32_t)FLT_BLOCK)), dim3(FLT_BLOCK), 0,
-                           P.stream, (const uint32_t *)W.off, (const uint32_t *)W.pkt, (const FilterResult *)W.res,
-                           o->lane_off_dev, o->lane_pkt_dev, S, o->lane_cap, tiles);
-        HIPC(c, hipGetLastError());
-        P.peered = true;
-    }
+    const udpdk_rx_lanes_t in = {o->meta_dev, bt->n, o->lane_off_dev, o->lane_pkt_dev, o->lane_cap, c->n_lanes};
+    if (c->drop_flags &&
+        (rc = sticky_stage(c, P, ST_DROP, o, [&](uint32_t *off, uint32_t *pkt) {
+             return filter_enqueue(c, P.flt, P.stream, &in, c->drop_flags, off, pkt, o->lane_cap);
+         })))
+        return rc;
+    if (!c->bal_on && !c->peer_on) return 0;
+    if (c->lane_mask != 0xFFFFFFFFu) return -EINVAL;           // compat mode: a lane is not a sockfd
+    if (c->bal_on &&
+        (rc = sticky_stage(c, P, ST_BALANCE, o, [&](uint32_t *off, uint32_t *pkt) {
+             return balance_enqueue(c, P.bal, P.stream, bt, &in, c->bal_rp, nullptr, off, pkt, o->lane_cap);
+         })))
+        return rc;
+    if (c->peer_on &&
+        (rc = sticky_stage(c, P, ST_PEER, o, [&](uint32_t *off, uint32_t *pkt) {
+             return peer_enqueue(c, P.peer, P.stream, bt, &in, c->peer_tab, off, pkt, o->lane_cap);
+         })))
+        return rc;
     return 0;
 }
 
@@ -1018,7 +977,7 @@ int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, con
     P.last_lane_cap = o->lane_cap;
     if (bt->n == 0) {
         HIPC(c, hipMemsetAsync(o->lane_off_dev, 0, (size_t)(S + 1) * 4, st));
-        HIPC(c, hipMemsetAsync(P.res, 0, sizeof(DevResult), st));
+        HIPC(c, hipMemsetAsync(P.res.dev, 0, sizeof(DevResult), st));
         P.last_tiles = 0;
         if (ts) c->n_sets_used--;                         // nothing was launched
         return 0;
@@ -1070,13 +1029,13 @@ int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, con
     }
     ra.spec_pkt = p.spec ? o->lane_pkt_dev : nullptr;          // see RxArgs::spec_pkt
     ra.spec_cap = p.spec ? o->lane_cap : 0u;
-    ra.spec_nonfull = p.spec ? P.res->nonfull : nullptr;
+    ra.spec_nonfull = p.spec ? P.res.dev->nonfull : nullptr;
     ra.spec_epoch = P.spec_epoch;
     ra.hint = c->hint;
     ra.seq = seq;
     ra.fuse = p.fuse ? P.fuse : nullptr;
     ra.lane_off = o->lane_off_dev;
-    ra.total = &P.res->total;
+    ra.total = &P.res.dev->total;
     ra.span = p.span ? 1u : 0u;
 
     if (ts) for (int k = 0; k < TIMED_KERNELS; ++k) ts->used[k] = false;
@@ -1089,20 +1048,20 @@ int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, con
         ca.tile_count = P.hist;
         ca.lane_pkt = o->lane_pkt_dev;
         ca.lane_off = o->lane_off_dev;
-        ca.total = &P.res->total;
+        ca.total = &P.res.dev->total;
         ca.n = bt->n;
         ca.tile_frames = p.T;
         ca.n_tiles = p.tiles;
         ca.lane_cap = o->lane_cap;
         ca.base = p.tile_base ? P.partial : nullptr;
         ca.spec = p.spec ? 1u : 0u;
-        ca.spec_nonfull = P.res->nonfull;
+        ca.spec_nonfull = P.res.dev->nonfull;
         ca.spec_epoch = P.spec_epoch;
         ca.hint = c->hint;
         ca.seq = seq;
         if (p.tile_base) {
             hipLaunchKernelGGL(rx_tile_base, dim3(1), dim3(1024), 0, st, (const uint32_t *)P.hist,
-                               P.partial, p.tiles);
+                               P.partial.p, p.tiles);
             HIPC(c, hipGetLastError());
         }
         HIPC(c, launch(st, ts, 2, true, true, rx_compact1, dim3(p.compact_grid), dim3(RX_BLOCK), 0u, ca));
@@ -1116,7 +1075,7 @@ int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, con
     sa.hist = P.hist;
     sa.partial = P.partial;
     sa.lane_off = o->lane_off_dev;
-    sa.total = &P.res->total;
+    sa.total = &P.res.dev->total;
     sa.n_elems = S * p.tiles;
     sa.n_tiles = p.tiles;
     sa.n_lanes = S;
@@ -1139,7 +1098,7 @@ int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, con
     ScatterArgs xa;
     xa.meta = o->meta_dev;
     xa.base = p.cols ? P.base : P.hist;
-    xa.total = &P.res->total;
+    xa.total = &P.res.dev->total;
     xa.frames = bt->frames_dev;
     xa.offset = bt->offset_dev;
     xa.port_tab = c->port_tab;
@@ -1201,36 +1160,30 @@ int enqueue_result(udpdk_gpu_ctx *c, Pipe &P)
     P.dirty = true;
     if (P.last_tiles) {
         hipLaunchKernelGGL(rx_counters, dim3(1), dim3(256), 0, P.stream, (const uint32_t *)P.tile_cnt,
-                           P.last_tiles, P.res->counters);
+                           P.last_tiles, P.res.dev->counters);
         HIPC(c, hipGetLastError());
     }
-    HIPC(c, hipMemcpyAsync(P.h_res, P.res, sizeof(DevResult), hipMemcpyDeviceToHost, P.stream));
-    if (P.filtered)
-        HIPC(c, hipMemcpyAsync(P.flt.h_res, P.flt.res, sizeof(FilterResult), hipMemcpyDeviceToHost, P.stream));
-    if (P.balanced)
-        HIPC(c, hipMemcpyAsync(P.bal.f.h_res, P.bal.f.res, sizeof(FilterResult), hipMemcpyDeviceToHost, P.stream));
-    if (P.peered)
-        HIPC(c, hipMemcpyAsync(P.peer.h_res, P.peer.res, sizeof(FilterResult), hipMemcpyDeviceToHost, P.stream));
-    return 0;
+    int rc = P.res.enqueue_fetch(c, P.stream);
+    for (int k = 0; k < N_STICKY && !rc; ++k)
+        if (P.sticky_ran[k]) rc = P.sticky[k]->res.enqueue_fetch(c, P.stream);
+    return rc;
 }
 
 int read_result(udpdk_gpu_ctx *c, Pipe &P, udpdk_rx_stats_t *st)
 {
-    for (int k = 0; k < UDPDK_N_COUNTERS; ++k) st->counters[k] = P.h_res->counters[k];
-    // (sticky drop mode: the kept count; overflow stays the pre-filter total's)
-    // (sticky balance mode: what it kept of that)
-    // (sticky peer filter: what it kept of that)
-    st->deliveries = P.peered     ? P.peer.h_res->kept
-                     : P.balanced ? P.bal.f.h_res->kept
-                     : P.filtered ? P.flt.h_res->kept
-                                  : P.h_res->total;
+    const DevResult *r = P.res.host;
+    for (int k = 0; k < UDPDK_N_COUNTERS; ++k) st->counters[k] = r->counters[k];
+    // (with sticky stages: what the last of them kept; overflow stays the pre-filter total's)
+    st->deliveries = r->total;
+    for (int k = 0; k < N_STICKY; ++k) {
+        const FilterResult *f = P.sticky[k]->res.host;
+        if (P.sticky_ran[k]) st->deliveries = f->kept;
+        P.removed[k] = P.sticky_ran[k] ? f->removed : 0u;
+    }
     for (Pipe &Q : c->pipes)
         if (Q.stats_of == st) Q.stats_of = nullptr;      // (a stats block reused across pipes)
     P.stats_of = st;
-    P.n_dropped = P.filtered ? P.flt.h_res->removed : 0u;
-    P.n_balanced = P.balanced ? P.bal.f.h_res->removed : 0u;
-    P.n_refused = P.peered ? P.peer.h_res->removed : 0u;
-    st->overflow = P.h_res->total > P.last_lane_cap ? 1u : 0u;
+    st->overflow = r->total > P.last_lane_cap ? 1u : 0u;
     return st->overflow ? -ENOSPC : 0;
 }
 
@@ -1272,12 +1225,9 @@ int enqueue_host(udpdk_gpu_ctx *c, int pipe, const uint8_t *frames_host, uint64_
     const bool pinned = n && hipPointerGetAttributes(&attr, frames_host - offset_base) == hipSuccess &&
                         attr.type == hipMemoryTypeHost;
     (void)hipGetLastError();
-    if ((rc = ensure_dev(c, (void **)&P.st_frames_d, &P.st_frames_dcap, fb))) return rc;
-    if (n && !pinned &&
-        (rc = ensure_host(c, (void **)&P.st_frames_h, &P.st_frames_hcap, fb))) return rc;
-    if ((rc = ensure_dev(c, (void **)&P.st_desc_d, &P.st_desc_dcap, desc))) return rc;
-    if ((rc = ensure_host(c, (void **)&P.st_desc_h, &P.st_desc_hcap, desc))) return rc;
-    if ((rc = ensure_dev(c, (void **)&P.st_out_d, &P.st_out_cap, outb))) return rc;
+    if ((rc = P.st_frames_d.ensure(c, fb)) || (n && !pinned && (rc = P.st_frames_h.ensure(c, fb))) ||
+        (rc = P.st_desc_d.ensure(c, desc)) || (rc = P.st_desc_h.ensure(c, desc)) || (rc = P.st_out_d.ensure(c, outb)))
+        return rc;
     const uint8_t *src = frames_host;
     if (n && !pinned) {
         memcpy(P.st_frames_h, frames_host, frames_bytes);
@@ -1296,12 +1246,12 @@ int enqueue_host(udpdk_gpu_ctx *c, int pipe, const uint8_t *frames_host, uint64_
     if (n) HIPC(c, hipMemcpyAsync(P.st_frames_d, src, frames_bytes, hipMemcpyHostToDevice, s));
     HIPC(c, hipMemcpyAsync(P.st_desc_d, dh, pt_off + (ptype_host ? (size_t)n * 4 : 0),
                            hipMemcpyHostToDevice, s));
-    uint32_t *meta_d = (uint32_t *)P.st_out_d;
+    uint32_t *meta_d = (uint32_t *)P.st_out_d.p;
     uint32_t *off_d = meta_d + n;
     uint32_t *pkt_d = off_d + c->n_lanes + 1;
-    udpdk_rx_batch_t b = {P.st_frames_d, frames_bytes, (const uint32_t *)P.st_desc_d,
-                          (const uint16_t *)(P.st_desc_d + (size_t)n * 4),
-                          ptype_host ? (const uint32_t *)(P.st_desc_d + pt_off) : nullptr, n};
+    const uint8_t *desc_d = P.st_desc_d;
+    udpdk_rx_batch_t b = {P.st_frames_d, frames_bytes, (const uint32_t *)desc_d, (const uint16_t *)(desc_d + (size_t)n * 4),
+                          ptype_host ? (const uint32_t *)(desc_d + pt_off) : nullptr, n};
     udpdk_rx_out_t o = {meta_d, off_d, pkt_d, lane_cap};
     if ((rc = rx_on_pipe(c, pipe, &b, &o))) return rc;
     if ((rc = enqueue_result(c, P))) return rc;
@@ -1355,15 +1305,63 @@ int udpdk_gpu_rx_host(udpdk_gpu_ctx *c, const uint8_t *frames_host, uint64_t fra
     return rc;
 }
 
+namespace {
+
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return na && nb && x < y + nb && y < x + na;
+}
+
+// What the three explicit lane-removal calls ask of the lane set and the outputs alike.
+int lanes_check(const udpdk_gpu_ctx *c, const udpdk_rx_lanes_t *in, const uint32_t *off_out, const uint32_t *pkt_out,
+                uint32_t out_cap)
+{
+    if (!c || !in || !off_out) return -EINVAL;
+    if (in->n_lanes == 0 || in->n_lanes > UDPDK_GPU_MAX_LANES || !in->lane_off_dev) return -EINVAL;
+    if ((in->lane_cap && !in->lane_pkt_dev) || (out_cap && !pkt_out)) return -EINVAL;
+    return 0;
+}
+
+// lanes_check, and what udpdk_gpu_rx_balance_select and udpdk_gpu_rx_peer_select ask besides: the
+// batch the lanes were made from, lanes that are sockets, outputs apart from the inputs.
+int select_check(const udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_lanes_t *in,
+                 const uint32_t *off_out, const uint32_t *pkt_out, uint32_t out_cap)
+{
+    if (!bt || lanes_check(c, in, off_out, pkt_out, out_cap)) return -EINVAL;
+    if (bt->n != in->n || bt->frames_bytes >= (1ull << 32)) return -EINVAL;
+    if (bt->n && (!bt->frames_dev || !bt->offset_dev)) return -EINVAL;
+    if (!c->have_snapshot || c->lane_mask != 0xFFFFFFFFu) return -EINVAL;
+    const size_t offb = ((size_t)in->n_lanes + 1) * 4, pktb = (size_t)in->lane_cap * 4;
+    if (ranges_overlap(off_out, offb, in->lane_off_dev, offb) || ranges_overlap(off_out, offb, in->lane_pkt_dev, pktb) ||
+        ranges_overlap(pkt_out, (size_t)out_cap * 4, in->lane_off_dev, offb) ||
+        ranges_overlap(pkt_out, (size_t)out_cap * 4, in->lane_pkt_dev, pktb))
+        return -EINVAL;
+    return 0;
+}
+
+// The FilterResult of W's last run into its mirror (and, for the balance stage, the count that goes
+// with it), waited for: what the three *_stats calls read.
+int fetch_filter_result(udpdk_gpu_ctx *c, FilterWs *W, BalanceWs *B = nullptr)
+{
+    if (!W) return -ENOENT;
+    HIPC(c, hipSetDevice(c->device));
+    const int rc = W->res.enqueue_fetch(c, W->stream);
+    if (rc) return rc;
+    if (B) HIPC(c, hipMemcpyAsync(B->h_cnt.p, B->cnt.p, 4, hipMemcpyDeviceToHost, W->stream));
+    HIPC(c, hipStreamSynchronize(W->stream));
+    return 0;
+}
+
+} // namespace
+
 int udpdk_gpu_rx_filter(udpdk_gpu_ctx *c, const udpdk_rx_lanes_t *in, uint32_t flags,
                         uint32_t *lane_off_out_dev, uint32_t *lane_pkt_out_dev, uint32_t out_cap)
 {
-    if (!c || !in || !lane_off_out_dev || (flags & ~UDPDK_RX_DROP_ALL)) return -EINVAL;
-    if (in->n_lanes == 0 || in->n_lanes > UDPDK_GPU_MAX_LANES || !in->lane_off_dev) return -EINVAL;
-    if ((in->lane_cap && !in->lane_pkt_dev) || (in->n && !in->meta_dev) || (out_cap && !lane_pkt_out_dev))
-        return -EINVAL;
-    HIPC(c, hipSetDevice(c->device));
-    if (c->depth > 1) { int r = join_pipes(c); if (r) return r; }
+    if ((flags & ~UDPDK_RX_DROP_ALL) || lanes_check(c, in, lane_off_out_dev, lane_pkt_out_dev, out_cap)) return -EINVAL;
+    if (in->n && !in->meta_dev) return -EINVAL;
+    const int rc = on_ctx_stream(c);
+    if (rc) return rc;
     return filter_enqueue(c, c->xflt, c->stream, in, flags, lane_off_out_dev, lane_pkt_out_dev, out_cap);
 }
 
@@ -1380,17 +1378,15 @@ int udpdk_gpu_rx_drop(udpdk_gpu_ctx *c, int flags)
 int udpdk_gpu_rx_drop_stats(udpdk_gpu_ctx *c, udpdk_rx_drop_stats_t *st)
 {
     if (!c || !st) return -EINVAL;
-    FilterWs *W = c->flt_last;
-    if (!W) return -ENOENT;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipMemcpyAsync(W->h_res, W->res, sizeof(FilterResult), hipMemcpyDeviceToHost, W->stream));
-    HIPC(c, hipStreamSynchronize(W->stream));
-    for (int k = 0; k < 4; ++k) st->dropped[k] = W->h_res->dropped[k];
-    st->kept = W->h_res->kept;
-    st->removed = W->h_res->removed;
-    st->bad_index = W->h_res->bad_index;
-    st->truncated = W->h_res->truncated;
-    return st->kept > W->out_cap ? -ENOSPC : 0;
+    const int rc = fetch_filter_result(c, c->flt_last);
+    if (rc) return rc;
+    const FilterResult *r = c->flt_last->res.host;
+    for (int k = 0; k < 4; ++k) st->dropped[k] = r->dropped[k];
+    st->kept = r->kept;
+    st->removed = r->removed;
+    st->bad_index = r->bad_index;
+    st->truncated = r->truncated;
+    return st->kept > c->flt_last->out_cap ? -ENOSPC : 0;
 }
 
 uint32_t udpdk_gpu_rx_balance_rank(uint32_t hash, uint32_t g)
@@ -1398,32 +1394,14 @@ uint32_t udpdk_gpu_rx_balance_rank(uint32_t hash, uint32_t g)
     return (uint32_t)(((uint64_t)hash * g) >> 32);
 }
 
-namespace {
-bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return na && nb && x < y + nb && y < x + na;
-}
-} // namespace
-
 int udpdk_gpu_rx_balance_select(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_lanes_t *in,
                                 const uint8_t *lane_rp_dev, const uint32_t *hash_dev,
                                 uint32_t *lane_off_out_dev, uint32_t *lane_pkt_out_dev, uint32_t out_cap)
 {
-    if (!c || !bt || !in || !lane_rp_dev || !lane_off_out_dev) return -EINVAL;
-    if (in->n_lanes == 0 || in->n_lanes > UDPDK_GPU_MAX_LANES || !in->lane_off_dev || !in->meta_dev) return -EINVAL;
-    if ((in->lane_cap && !in->lane_pkt_dev) || (out_cap && !lane_pkt_out_dev)) return -EINVAL;
-    if (bt->n != in->n || bt->frames_bytes >= (1ull << 32)) return -EINVAL;
-    if (bt->n && (!bt->frames_dev || !bt->offset_dev)) return -EINVAL;
-    if (!c->have_snapshot || c->lane_mask != 0xFFFFFFFFu) return -EINVAL;
-    const size_t offb = ((size_t)in->n_lanes + 1) * 4;
-    if (ranges_overlap(lane_off_out_dev, offb, in->lane_off_dev, offb) ||
-        ranges_overlap(lane_off_out_dev, offb, in->lane_pkt_dev, (size_t)in->lane_cap * 4) ||
-        ranges_overlap(lane_pkt_out_dev, (size_t)out_cap * 4, in->lane_off_dev, offb) ||
-        ranges_overlap(lane_pkt_out_dev, (size_t)out_cap * 4, in->lane_pkt_dev, (size_t)in->lane_cap * 4))
-        return -EINVAL;
-    HIPC(c, hipSetDevice(c->device));
-    if (c->depth > 1) { int r = join_pipes(c); if (r) return r; }
+    if (!lane_rp_dev || select_check(c, bt, in, lane_off_out_dev, lane_pkt_out_dev, out_cap)) return -EINVAL;
+    if (!in->meta_dev) return -EINVAL;
+    const int rc = on_ctx_stream(c);
+    if (rc) return rc;
     return balance_enqueue(c, c->xbal, c->stream, bt, in, lane_rp_dev, hash_dev, lane_off_out_dev,
                            lane_pkt_out_dev, out_cap);
 }
@@ -1437,7 +1415,7 @@ int udpdk_gpu_rx_balance(udpdk_gpu_ctx *c, const uint8_t *lane_rp_host, uint32_t
         c->bal_on = false;
         return 0;
     }
-    if (!c->bal_rp) HIPC(c, hipMalloc((void **)&c->bal_rp, c->max_lanes));
+    { int rc = c->bal_rp.ensure(c, c->max_lanes); if (rc) return rc; }
     std::vector<uint8_t> rp(c->max_lanes, 0);
     for (uint32_t l = 0; l < n_lanes; ++l) rp[l] = lane_rp_host[l] ? 1 : 0;
     HIPC(c, hipMemcpy(c->bal_rp, rp.data(), rp.size(), hipMemcpyHostToDevice));
@@ -1452,18 +1430,15 @@ int udpdk_gpu_rx_balance_stats(udpdk_gpu_ctx *c, udpdk_rx_balance_stats_t *st)
 {
     if (!c || !st) return -EINVAL;
     BalanceWs *B = c->bal_last;
-    if (!B) return -ENOENT;
-    FilterWs *W = &B->f;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipMemcpyAsync(W->h_res, W->res, sizeof(FilterResult), hipMemcpyDeviceToHost, W->stream));
-    HIPC(c, hipMemcpyAsync(B->h_cnt, B->cnt, 4, hipMemcpyDeviceToHost, W->stream));
-    HIPC(c, hipStreamSynchronize(W->stream));
-    st->kept = W->h_res->kept;
-    st->removed = W->h_res->removed;
+    const int rc = fetch_filter_result(c, B, B);
+    if (rc) return rc;
+    const FilterResult *r = B->res.host;
+    st->kept = r->kept;
+    st->removed = r->removed;
     st->balanced = *B->h_cnt;
-    st->bad_index = W->h_res->bad_index;
-    st->truncated = W->h_res->truncated;
-    return st->kept > W->out_cap ? -ENOSPC : 0;
+    st->bad_index = r->bad_index;
+    st->truncated = r->truncated;
+    return st->kept > B->out_cap ? -ENOSPC : 0;
 }
 
 int udpdk_gpu_rx_removed(udpdk_gpu_ctx *c, const udpdk_rx_stats_t *stats, uint32_t *dropped, uint32_t *balanced)
@@ -1471,8 +1446,8 @@ int udpdk_gpu_rx_removed(udpdk_gpu_ctx *c, const udpdk_rx_stats_t *stats, uint32
     if (!c || !stats || !dropped || !balanced) return -EINVAL;
     for (const Pipe &P : c->pipes) {
         if (P.stats_of != stats) continue;
-        *dropped = P.n_dropped;
-        *balanced = P.n_balanced;
+        *dropped = P.removed[ST_DROP];
+        *balanced = P.removed[ST_BALANCE];
         return 0;
     }
     return -ENOENT;
@@ -1482,21 +1457,11 @@ int udpdk_gpu_rx_peer_select(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const
                              const udpdk_peer_t *peer_dev, uint32_t *lane_off_out_dev,
                              uint32_t *lane_pkt_out_dev, uint32_t out_cap)
 {
-    if (!c || !bt || !in || !peer_dev || !lane_off_out_dev) return -EINVAL;
-    if (((uintptr_t)peer_dev & 7u) != 0) return -EINVAL;               // (the records load as 8-byte words)
-    if (in->n_lanes == 0 || in->n_lanes > UDPDK_GPU_MAX_LANES || !in->lane_off_dev) return -EINVAL;
-    if ((in->lane_cap && !in->lane_pkt_dev) || (out_cap && !lane_pkt_out_dev)) return -EINVAL;
-    if (bt->n != in->n || bt->frames_bytes >= (1ull << 32)) return -EINVAL;
-    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
-    if (!c->have_snapshot || c->lane_mask != 0xFFFFFFFFu) return -EINVAL;
-    const size_t offb = ((size_t)in->n_lanes + 1) * 4;
-    if (ranges_overlap(lane_off_out_dev, offb, in->lane_off_dev, offb) ||
-        ranges_overlap(lane_off_out_dev, offb, in->lane_pkt_dev, (size_t)in->lane_cap * 4) ||
-        ranges_overlap(lane_pkt_out_dev, (size_t)out_cap * 4, in->lane_off_dev, offb) ||
-        ranges_overlap(lane_pkt_out_dev, (size_t)out_cap * 4, in->lane_pkt_dev, (size_t)in->lane_cap * 4))
-        return -EINVAL;
-    HIPC(c, hipSetDevice(c->device));
-    if (c->depth > 1) { int r = join_pipes(c); if (r) return r; }
+    if (!peer_dev || ((uintptr_t)peer_dev & 7u) != 0) return -EINVAL;   // (the records load as 8-byte words)
+    if (select_check(c, bt, in, lane_off_out_dev, lane_pkt_out_dev, out_cap)) return -EINVAL;
+    if (bt->n && !bt->length_dev) return -EINVAL;
+    const int rc = on_ctx_stream(c);
+    if (rc) return rc;
     return peer_enqueue(c, c->xpeer, c->stream, bt, in, reinterpret_cast<const uint2 *>(peer_dev),
                         lane_off_out_dev, lane_pkt_out_dev, out_cap);
 }
@@ -1512,7 +1477,7 @@ int udpdk_gpu_rx_peer(udpdk_gpu_ctx *c, const udpdk_peer_t *peer_host, uint32_t 
         c->peer_on = false;
         return 0;
     }
-    if (!c->peer_tab) HIPC(c, hipMalloc((void **)&c->peer_tab, (size_t)c->max_lanes * sizeof(uint2)));
+    { int rc = c->peer_tab.ensure(c, c->max_lanes); if (rc) return rc; }
     std::vector<uint2> tab(c->max_lanes, make_uint2(0u, 0u));
     for (uint32_t l = 0; l < n_lanes; ++l)
         if (peer_host[l].on) tab[l] = make_uint2(peer_host[l].ip, (uint32_t)peer_host[l].port | (1u << 16));
@@ -1524,18 +1489,16 @@ int udpdk_gpu_rx_peer(udpdk_gpu_ctx *c, const udpdk_peer_t *peer_host, uint32_t 
 int udpdk_gpu_rx_peer_stats(udpdk_gpu_ctx *c, udpdk_rx_peer_stats_t *st)
 {
     if (!c || !st) return -EINVAL;
-    FilterWs *W = c->peer_last;
-    if (!W) return -ENOENT;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipMemcpyAsync(W->h_res, W->res, sizeof(FilterResult), hipMemcpyDeviceToHost, W->stream));
-    HIPC(c, hipStreamSynchronize(W->stream));
-    st->kept = W->h_res->kept;
-    st->removed = W->h_res->removed;
-    st->refused = (uint32_t)W->h_res->dropped[0];
-    st->bad_frame = (uint32_t)W->h_res->dropped[1];
-    st->bad_index = W->h_res->bad_index;
-    st->truncated = W->h_res->truncated;
-    return st->kept > W->out_cap ? -ENOSPC : 0;
+    const int rc = fetch_filter_result(c, c->peer_last);
+    if (rc) return rc;
+    const FilterResult *r = c->peer_last->res.host;
+    st->kept = r->kept;
+    st->removed = r->removed;
+    st->refused = (uint32_t)r->dropped[0];
+    st->bad_frame = (uint32_t)r->dropped[1];
+    st->bad_index = r->bad_index;
+    st->truncated = r->truncated;
+    return st->kept > c->peer_last->out_cap ? -ENOSPC : 0;
 }
 
 int udpdk_gpu_rx_peer_removed(udpdk_gpu_ctx *c, const udpdk_rx_stats_t *stats, uint32_t *refused)
@@ -1543,7 +1506,7 @@ int udpdk_gpu_rx_peer_removed(udpdk_gpu_ctx *c, const udpdk_rx_stats_t *stats, u
     if (!c || !stats || !refused) return -EINVAL;
     for (const Pipe &P : c->pipes) {
         if (P.stats_of != stats) continue;
-        *refused = P.n_refused;
+        *refused = P.removed[ST_PEER];
         return 0;
     }
     return -ENOENT;
@@ -1597,11 +1560,15 @@ static int rx_gather_launch(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const 
     if (!slot_off_dev && (o->slot_bytes < 16u || (o->slot_bytes & 15u))) return -EINVAL;
     if ((uintptr_t)o->payload_dev & 15u) return -EINVAL;
     if (bt->frames_bytes >= (1ull << 32) || (uint64_t)first + count > 0xFFFFFFFFull) return -EINVAL;
-    HIPC(c, hipSetDevice(c->device));
     // pipe >= 0: on that pipe's stream, after its own work only (udpdk_gpu_pipe_gather_packed)
-    if (pipe < 0 && c->depth > 1) { int r = join_pipes(c); if (r) return r; }
+    if (pipe < 0) {
+        const int rc = on_ctx_stream(c);
+        if (rc) return rc;
+    } else {
+        HIPC(c, hipSetDevice(c->device));
+        c->pipes[pipe].dirty = true;
+    }
     const hipStream_t gst = pipe < 0 ? c->stream : c->pipes[pipe].stream;
-    if (pipe >= 0) c->pipes[pipe].dirty = true;
     GatherArgs ga;
     ga.frames = bt->frames_dev;
     ga.offset = bt->offset_dev;
@@ -1730,14 +1697,14 @@ int udpdk_gpu_rss_config(udpdk_gpu_ctx *c, const udpdk_rss_conf_t *conf)
     { int r = join_pipes(c); if (r) return r; }
     HIPC(c, hipStreamSynchronize(c->stream));
     const uint32_t tiles = ceil_div(std::max<uint32_t>(c->max_frames, 1), RSS_TILE);
-    if (!c->rss_reta) {
-        HIPC(c, hipMalloc((void **)&c->rss_reta, RSS_RETA_MAX * sizeof(uint16_t)));
-        HIPC(c, hipMalloc((void **)&c->rss_ktab, 12 * 256 * sizeof(uint32_t)));
-        HIPC(c, hipMalloc((void **)&c->rss_qid, std::max<uint32_t>(c->max_frames, 1)));
-        HIPC(c, hipMalloc((void **)&c->rss_hist, (size_t)tiles * RSS_MAX_QUEUES * 4));
-        HIPC(c, hipMalloc((void **)&c->rss_partial, (size_t)ceil_div(tiles, SCAN_COL_CHUNK) * RSS_MAX_QUEUES * 4));
-        HIPC(c, hipMalloc((void **)&c->rss_total, 64));
-        HIPC(c, hipMalloc((void **)&c->rss_fuse, FUSE_BYTES));
+    if (!c->rss_fuse) {
+        int rc;
+        if ((rc = c->rss_reta.ensure(c, RSS_RETA_MAX)) || (rc = c->rss_ktab.ensure(c, 12 * 256)) ||
+            (rc = c->rss_qid.ensure(c, std::max<uint32_t>(c->max_frames, 1))) ||
+            (rc = c->rss_hist.ensure(c, (size_t)tiles * RSS_MAX_QUEUES)) ||
+            (rc = c->rss_partial.ensure(c, (size_t)ceil_div(tiles, SCAN_COL_CHUNK) * RSS_MAX_QUEUES)) ||
+            (rc = c->rss_total.ensure(c, 64 / 4)) || (rc = c->rss_fuse.ensure(c, FUSE_BYTES / 8)))
+            return rc;
         HIPC(c, hipMemset(c->rss_fuse, 0, FUSE_BYTES));
     }
     {
@@ -1822,8 +1789,8 @@ int udpdk_gpu_rss(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rss_
     if (fuse) {
         // (the bases were written by rss_hash's last workgroup)
     } else if (a.qmajor) {
-        hipLaunchKernelGGL(rss_base, dim3(1), dim3(1024), 0, st, c->rss_hist, tiles * S, tiles,
-                           o->queue_off_dev, c->rss_total);
+        hipLaunchKernelGGL(rss_base, dim3(1), dim3(1024), 0, st, c->rss_hist.p, tiles * S, tiles,
+                           o->queue_off_dev, c->rss_total.p);
     } else {
         const uint32_t nc = ceil_div(tiles, SCAN_COL_CHUNK);
         const dim3 grid(nc, ceil_div(S, (uint32_t)SCAN_BLOCK));
@@ -1909,8 +1876,7 @@ int udpdk_gpu_tx_build_flags(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
     if (!c->slots || !c->n_slots) return -EINVAL;
     if (bt->payload_bytes >= (1ull << 32) || o->frames_bytes >= (1ull << 32)) return -EINVAL;
     if (((uintptr_t)o->frames_dev & 15u) || ((uintptr_t)bt->payload_dev & 15u)) return -EINVAL;
-    HIPC(c, hipSetDevice(c->device));
-    if (c->depth > 1) { int r = join_pipes(c); if (r) return r; }
+    { int r = on_ctx_stream(c); if (r) return r; }
     TxArgs ta;
     ta.payload = bt->payload_dev;
     ta.payload_off = bt->payload_off_dev;
@@ -1979,11 +1945,7 @@ int reply_enqueue(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_l
     ReplyWs &W = c->rpl;
     const uint32_t nb = ceil_div(count, RPL_TILE);
     int rc;
-    if ((rc = ensure_dev(c, (void **)&W.row, &W.row_cap, (size_t)nb * RPL_ROW * 4)) ||
-        (rc = ensure_dev(c, (void **)&W.base, &W.base_cap, (size_t)nb * 8)) ||
-        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(ReplyResult))) ||
-        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(ReplyResult))))
-        return rc;
+    if ((rc = W.row.ensure(c, (size_t)nb * RPL_ROW)) || (rc = W.base.ensure(c, nb)) || (rc = W.res.ensure(c))) return rc;
     ReplyArgs ra;
     ra.frames = bt->frames_dev;
     ra.offset = bt->offset_dev;
@@ -1999,7 +1961,7 @@ int reply_enqueue(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_l
     ra.frame_off = pl->frame_off_dev;
     ra.row = W.row;
     ra.base = W.base;
-    ra.res = W.res;
+    ra.res = W.res.dev;
     ra.first = first;
     ra.count = count;
     ra.n = bt->n;
@@ -2017,7 +1979,7 @@ int reply_enqueue(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_l
     hipLaunchKernelGGL(tx_reply_place, dim3((uint32_t)(((uint64_t)count + RPL_TILE) / RPL_TILE)),
                        dim3(RPL_BLOCK), 0, c->stream, ra);
     HIPC(c, hipGetLastError());
-    W.ran = true;
+    W.res.ran = true;
     return 0;
 }
 
@@ -2037,8 +1999,7 @@ int udpdk_gpu_tx_reply_plan(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const 
 {
     int rc = reply_check(c, bt, lanes, first, count, mtu, out_cap, pl);
     if (rc || !count) return rc;
-    HIPC(c, hipSetDevice(c->device));
-    if (c->depth > 1 && (rc = join_pipes(c))) return rc;
+    if ((rc = on_ctx_stream(c))) return rc;
     return reply_enqueue(c, bt, lanes, first, count, lane_sel_dev, mtu, out_cap, pl);
 }
 
@@ -2052,8 +2013,7 @@ int udpdk_gpu_tx_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udp
     if (rc) return rc;
     if (((uintptr_t)frames_out_dev & 15u) || ((uintptr_t)bt->frames_dev & 15u)) return -EINVAL;
     if (!count) return 0;
-    HIPC(c, hipSetDevice(c->device));
-    if (c->depth > 1 && (rc = join_pipes(c))) return rc;
+    if ((rc = on_ctx_stream(c))) return rc;
     if ((rc = reply_enqueue(c, bt, lanes, first, count, lane_sel_dev, mtu, out_cap, pl))) return rc;
     const udpdk_tx_batch_t tb = {bt->frames_dev, bt->frames_bytes, pl->payload_off_dev, pl->payload_len_dev,
                                  pl->sockfd_dev, pl->dst_ip_dev, pl->dst_port_dev, count};
@@ -2064,18 +2024,16 @@ int udpdk_gpu_tx_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udp
 int udpdk_gpu_tx_reply_stats(udpdk_gpu_ctx *c, udpdk_tx_reply_stats_t *st)
 {
     if (!c || !st) return -EINVAL;
-    ReplyWs &W = c->rpl;
-    if (!W.ran) return -ENOENT;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipMemcpyAsync(W.h_res, W.res, sizeof(ReplyResult), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    st->bytes_needed = W.h_res->bytes_needed;
-    st->replied = W.h_res->replied;
-    st->skipped = W.h_res->skipped;
-    st->bad_index = W.h_res->bad_index;
-    st->unselected = W.h_res->unselected;
-    st->no_room = W.h_res->no_room;
-    st->frames = W.h_res->frames;
+    const int rc = ctx_result(c, c->rpl.res);
+    if (rc) return rc;
+    const ReplyResult *r = c->rpl.res.host;
+    st->bytes_needed = r->bytes_needed;
+    st->replied = r->replied;
+    st->skipped = r->skipped;
+    st->bad_index = r->bad_index;
+    st->unselected = r->unselected;
+    st->no_room = r->no_room;
+    st->frames = r->frames;
     return st->no_room ? -ENOSPC : 0;
 }
 
@@ -2109,16 +2067,13 @@ int icmp_enqueue(udpdk_gpu_ctx *c, IcmpWs &W, hipStream_t st, const udpdk_tx_con
     const uint32_t nb = ceil_div(bt->n, ICMP_TILE);
     const size_t rows = std::max<size_t>(ceil_div(std::max(bt->n, c->max_frames), ICMP_TILE), 1);
     int rc;
-    if ((rc = ensure_dev(c, (void **)&W.cand, &W.cand_cap, rows * ICMP_TILE * sizeof(IcmpEntry))) ||
-        (rc = ensure_dev(c, (void **)&W.row, &W.row_cap, rows * (ICMP_ROW + 2) * 4)) ||
-        (rc = ensure_dev(c, (void **)&W.bbase, &W.bbase_cap, rows * 8)) ||
-        (rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(IcmpResult))) ||
-        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(IcmpResult))))
+    if ((rc = W.cand.ensure(c, rows * ICMP_TILE)) || (rc = W.row.ensure(c, rows * (ICMP_ROW + 2))) ||
+        (rc = W.bbase.ensure(c, rows)) || (rc = W.res.ensure(c)))
         return rc;
     if (!bt->n) {
         HIPC(c, hipMemsetAsync(o->reply_off_dev, 0, 4, st));
-        HIPC(c, hipMemsetAsync(W.res, 0, sizeof(IcmpResult), st));
-        W.ran = true;
+        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(IcmpResult), st));
+        W.res.ran = true;
         return 0;
     }
     IcmpArgs ia;
@@ -2134,7 +2089,7 @@ int icmp_enqueue(udpdk_gpu_ctx *c, IcmpWs &W, hipStream_t st, const udpdk_tx_con
     ia.ubase = W.row + (size_t)ICMP_ROW * nb;
     ia.rbase = ia.ubase + nb;
     ia.bbase = W.bbase;
-    ia.res = W.res;
+    ia.res = W.res.dev;
     ia.n = bt->n;
     ia.n_blocks = nb;
     ia.frames_bytes = (uint32_t)bt->frames_bytes;
@@ -2155,7 +2110,7 @@ int icmp_enqueue(udpdk_gpu_ctx *c, IcmpWs &W, hipStream_t st, const udpdk_tx_con
     HIPC(c, hipGetLastError());
     hipLaunchKernelGGL(icmp_build, dim3(nb), dim3(ICMP_BLOCK), 0, st, ia);
     HIPC(c, hipGetLastError());
-    W.ran = true;
+    W.res.ran = true;
     return 0;
 }
 
@@ -2188,20 +2143,15 @@ int udpdk_gpu_icmp_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const u
 {
     int rc = icmp_check(c, cfg, bt, meta_dev, flags, mtu, o);
     if (rc) return rc;
-    HIPC(c, hipSetDevice(c->device));
-    if (c->depth > 1 && (rc = join_pipes(c))) return rc;
+    if ((rc = on_ctx_stream(c))) return rc;
     return icmp_enqueue(c, c->icmp, c->stream, cfg, bt, meta_dev, flags, mtu, err_limit, o);
 }
 
 int udpdk_gpu_icmp_stats(udpdk_gpu_ctx *c, udpdk_icmp_stats_t *st)
 {
     if (!c || !st) return -EINVAL;
-    IcmpWs &W = c->icmp;
-    if (!W.ran) return -ENOENT;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipMemcpyAsync(W.h_res, W.res, sizeof(IcmpResult), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    return icmp_stats_out(W.h_res, st);
+    const int rc = ctx_result(c, c->icmp.res);
+    return rc ? rc : icmp_stats_out(c->icmp.res.host, st);
 }
 
 int udpdk_gpu_pipe_icmp_reply(udpdk_gpu_ctx *c, int pipe, const udpdk_tx_config_t *cfg,
@@ -2216,16 +2166,14 @@ int udpdk_gpu_pipe_icmp_reply(udpdk_gpu_ctx *c, int pipe, const udpdk_tx_config_
     P.dirty = true;
     if ((rc = icmp_enqueue(c, P.icmp, P.stream, cfg, bt, meta_dev, flags, mtu, err_limit, o))) return rc;
     // the counts follow on the pipe's stream: udpdk_gpu_pipe_icmp_stats reads them after udpdk_gpu_pipe_wait
-    HIPC(c, hipMemcpyAsync(P.icmp.h_res, P.icmp.res, sizeof(IcmpResult), hipMemcpyDeviceToHost, P.stream));
-    return 0;
+    return P.icmp.res.enqueue_fetch(c, P.stream);
 }
 
 int udpdk_gpu_pipe_icmp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_icmp_stats_t *st)
 {
     if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    const IcmpWs &W = c->pipes[pipe].icmp;
-    if (!W.ran) return -ENOENT;
-    return icmp_stats_out(W.h_res, st);
+    const ResultSlot<IcmpResult> &R = c->pipes[pipe].icmp.res;
+    return R.ran ? icmp_stats_out(R.host, st) : -ENOENT;
 }
 
 namespace {
@@ -2249,12 +2197,10 @@ int icmp_err_enqueue(udpdk_gpu_ctx *c, IcmpErrWs &W, hipStream_t st, uint32_t ou
                      const uint32_t *meta_dev, const udpdk_peer_t *peer_dev, uint32_t n_lanes, uint64_t *err_dev)
 {
     int rc;
-    if ((rc = ensure_dev(c, (void **)&W.res, &W.res_cap, sizeof(IcmpErrResult))) ||
-        (rc = ensure_host(c, (void **)&W.h_res, &W.h_res_cap, sizeof(IcmpErrResult))))
-        return rc;
+    if ((rc = W.ensure(c))) return rc;
     unsigned long long *err = reinterpret_cast<unsigned long long *>(err_dev);
     hipLaunchKernelGGL(icmp_err_clear, dim3(ceil_div(std::max(n_lanes, ICMP_ERR_ROW + 1u), (uint32_t)ICMP_ERR_BLOCK)),
-                       dim3(ICMP_ERR_BLOCK), 0, st, err, n_lanes, W.res);
+                       dim3(ICMP_ERR_BLOCK), 0, st, err, n_lanes, W.dev.p);
     HIPC(c, hipGetLastError());
     W.ran = true;
     if (!bt->n) return 0;
@@ -2268,7 +2214,7 @@ int icmp_err_enqueue(udpdk_gpu_ctx *c, IcmpErrWs &W, hipStream_t st, uint32_t ou
     // the sticky table holds max_lanes records, off past what udpdk_gpu_rx_peer was given
     ea.peer = peer_dev ? reinterpret_cast<const uint2 *>(peer_dev) : c->peer_tab;
     ea.err = err;
-    ea.res = W.res;
+    ea.res = W.dev;
     ea.n = bt->n;
     ea.frames_bytes = (uint32_t)bt->frames_bytes;
     ea.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
@@ -2298,21 +2244,16 @@ int udpdk_gpu_icmp_errors(udpdk_gpu_ctx *c, uint32_t our_ip, const udpdk_rx_batc
 {
     int rc = icmp_err_check(c, bt, meta_dev, peer_dev, n_lanes, err_dev);
     if (rc) return rc;
-    HIPC(c, hipSetDevice(c->device));
-    if (c->depth > 1 && (rc = join_pipes(c))) return rc;
+    if ((rc = on_ctx_stream(c))) return rc;
     return icmp_err_enqueue(c, c->icmp_err, c->stream, our_ip, bt, meta_dev, peer_dev, n_lanes, err_dev);
 }
 
 int udpdk_gpu_icmp_err_stats(udpdk_gpu_ctx *c, udpdk_icmp_err_stats_t *st)
 {
     if (!c || !st) return -EINVAL;
-    IcmpErrWs &W = c->icmp_err;
-    if (!W.ran) return -ENOENT;
-    HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipMemcpyAsync(W.h_res, W.res, sizeof(IcmpErrResult), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    icmp_err_stats_out(W.h_res, st);
-    return 0;
+    const int rc = ctx_result(c, c->icmp_err);
+    if (!rc) icmp_err_stats_out(c->icmp_err.host, st);
+    return rc;
 }
 
 int udpdk_gpu_pipe_icmp_errors(udpdk_gpu_ctx *c, int pipe, uint32_t our_ip, const udpdk_rx_batch_t *bt,
@@ -2327,8 +2268,7 @@ int udpdk_gpu_pipe_icmp_errors(udpdk_gpu_ctx *c, int pipe, uint32_t our_ip, cons
     P.dirty = true;
     if ((rc = icmp_err_enqueue(c, P.icmp_err, P.stream, our_ip, bt, meta_dev, peer_dev, n_lanes, err_dev))) return rc;
     // the counts follow on the pipe's stream: udpdk_gpu_pipe_icmp_err_stats reads them after udpdk_gpu_pipe_wait
-    HIPC(c, hipMemcpyAsync(P.icmp_err.h_res, P.icmp_err.res, sizeof(IcmpErrResult), hipMemcpyDeviceToHost, P.stream));
-    return 0;
+    return P.icmp_err.enqueue_fetch(c, P.stream);
 }
 
 int udpdk_gpu_pipe_icmp_err_stats(udpdk_gpu_ctx *c, int pipe, udpdk_icmp_err_stats_t *st)
@@ -2336,7 +2276,7 @@ int udpdk_gpu_pipe_icmp_err_stats(udpdk_gpu_ctx *c, int pipe, udpdk_icmp_err_sta
     if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
     const IcmpErrWs &W = c->pipes[pipe].icmp_err;
     if (!W.ran) return -ENOENT;
-    icmp_err_stats_out(W.h_res, st);
+    icmp_err_stats_out(W.host, st);
     return 0;
 }
 
