@@ -127,8 +127,8 @@ int udpdk_poll_echo(const uint8_t *frames, uint64_t frames_bytes, const uint32_t
                     uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *out_len,
                     uint32_t max, uint32_t *n_out, udpdk_rx_stats_t *stats);
 
-/* Datagrams waiting in the TX rings, plus the ICMP frames queued for the next drain
- * (udpdk_config_icmp). */
+/* Datagrams waiting in the TX rings, plus the ICMP and ARP frames queued for the next drain
+ * (udpdk_config_icmp, udpdk_config_arp, udpdk_arp_announce). */
 uint64_t udpdk_tx_pending(void);
 
 /* Datagrams udpdk_tx_drain dropped because they needed more frames or bytes than a drain with
@@ -343,6 +343,38 @@ typedef struct {
     uint64_t errors, msg_bad, quote_bad, soft, no_socket, reported, posted;
 } udpdk_icmp_err_counts_t;
 int udpdk_icmp_err_counts(udpdk_icmp_err_counts_t *counts);
+
+/* ARP replies (ini: [gpu] arp = 0 | 1; default 0: as in the reference, a who-has request for our
+ * address ends as NOT_IPV4 and is forgotten, so a peer needs a static neighbour entry for us). With 1,
+ * udpdk_poll_rx runs udpdk_gpu_arp_reply (udpdk_gpu.h) on every staged batch whose RX counters show a
+ * frame that is not IPv4, before the ICMP stage: every valid request for our address (the library's
+ * source address, asked by a unicast sender that is not us and does not claim our address) is answered
+ * with the library's MAC, unicast to the asker. A batch of pure IPv4 costs nothing. The replies, 42
+ * bytes each in arrival order, go onto the host queue of the ICMP answers (at most 4096 frames; what a
+ * full queue drops counts in udpdk_icmp_counts().queue_dropped, and requests beyond 4096 in one batch
+ * as no_room), so udpdk_tx_drain emits a poll's ARP replies first, then its ICMP answers, then the
+ * socket datagrams, and udpdk_tx_pending counts them. The one-piece and the chunked poll answer (a
+ * chunk on its pipe, replies queued in chunk order); udpdk_poll_echo does not. Sharded polls do not
+ * answer: there on = 1 gives -1 with ENOTSUP and udpdk_init fails on such an ini, as for
+ * udpdk_config_icmp. With no source address configured nothing is answered. With the loopback port our
+ * own replies come back as other_op and our announcement as own: nothing is answered twice. Not done:
+ * a neighbour cache, sending requests, resolving the destination MAC of what we send (still the
+ * configured [port0_dst] MAC), defending our address, VLAN tags. Returns the value in force before
+ * the call; a negative argument only reads it; above 1: -1, EINVAL. */
+int udpdk_config_arp(int on);
+/* Queue one RFC 5227 announcement of our address (a broadcast request with sender and target address
+ * both ours, built on the host) for the next udpdk_tx_drain (ini: [gpu] arp_announce = 1 makes
+ * udpdk_init call it once). Needs no GPU. 0, or -1 with EADDRNOTAVAIL (no source address configured)
+ * or ENOBUFS (the queue dropped it). */
+int udpdk_arp_announce(void);
+/* Session sums over polls, like udpdk_icmp_counts: the batches or chunks the stage ran on (scanned),
+ * the device stage's counts (udpdk_arp_stats_t without bad_frame) and the announcements queued.
+ * udpdk_host_reset zeroes them. */
+typedef struct {
+    uint64_t scanned, arp, malformed, other_op, own, sender_bad, not_ours, conflict, eligible, replies, no_room,
+             announced;
+} udpdk_arp_counts_t;
+int udpdk_arp_counts(udpdk_arp_counts_t *counts);
 
 /* Socket slot state (exch_slot_info, udpdk_types.h:40-47) for the GPU TX slot table. */
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots);

@@ -55,7 +55,9 @@ extern "C" {
  *    (still 3: udpdk_gpu_icmp_reply / udpdk_gpu_icmp_stats / udpdk_gpu_icmp_geometry /
  *    udpdk_gpu_pipe_icmp_reply / udpdk_gpu_pipe_icmp_stats were added)
  *    (still 3: udpdk_gpu_icmp_errors / udpdk_gpu_icmp_err_stats / udpdk_gpu_pipe_icmp_errors /
- *    udpdk_gpu_pipe_icmp_err_stats / udpdk_gpu_icmp_errno were added) */
+ *    udpdk_gpu_pipe_icmp_err_stats / udpdk_gpu_icmp_errno were added)
+ *    (still 3: udpdk_gpu_arp_reply / udpdk_gpu_arp_stats / udpdk_gpu_arp_geometry /
+ *    udpdk_gpu_pipe_arp_reply / udpdk_gpu_pipe_arp_stats were added) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -942,6 +944,91 @@ int udpdk_gpu_pipe_icmp_err_stats(udpdk_gpu_ctx *ctx, int pipe, udpdk_icmp_err_s
 /* The errno of destination-unreachable code `code` (0: none, codes above 15) and, when hard is not
  * NULL, whether the error is hard (1) or soft (0). Host only. */
 int udpdk_gpu_icmp_errno(uint32_t code, int *hard);
+
+/* ---------------------------------------------------------------------------------------------
+ * ARP on the device: answers to who-has requests for the stack's own address (RFC 826). The
+ * reference has no ARP (its .ini carries the peer's MAC by hand): a request ends as
+ * UDPDK_V_NOT_IPV4 and nothing looks at it again, so no on-link host can learn our MAC. This optional
+ * stage after udpdk_gpu_rx answers from what is already in device memory (the verdict words, the
+ * staged frames). Parity is against RFC 826 and RFC 5227. Off unless called.
+ *
+ * All addresses are raw. The first failing step decides the single counter a frame lands in.
+ *   1. Candidate by meta: verdict UDPDK_V_NOT_IPV4. For any other frame no descriptor and no frame
+ *      byte is read, so a batch of IPv4 costs the read of meta.
+ *   2. Frame gate: length[i] >= 42 and offset[i] + length[i] <= frames_bytes (64 bits), else the
+ *      candidate counts as bad_frame and no frame byte is read (meta need not come from this batch).
+ *   3. Bytes 12-13 == 08 06, else the frame is counted nowhere (IPv6, LLDP, ...). Then arp++.
+ *   4. Bytes 14-19 == 00 01 08 00 06 04 (Ethernet, IPv4, lengths 6 and 4), else malformed.
+ *   5. Bytes 20-21 == 00 01 (request), else other_op.
+ *   6. Sender hardware address, bytes 22-27: equal to cfg->src_mac: own; byte 22 odd (the group
+ *      bit) or all six bytes zero: sender_bad.
+ *   7. Target address, bytes 38-41, == cfg->src_ip, else not_ours.
+ *   8. Sender address, bytes 28-31, == cfg->src_ip: conflict, not answered (defending an address,
+ *      RFC 5227 §2.4, is out of scope; the counter lets an operator see it). A sender address of
+ *      0.0.0.0, an RFC 5227 probe, is answered.
+ *   9. Eligible. Frames longer than 42 bytes (Ethernet padding to 60) are accepted and bytes past
+ *      41 ignored. The Ethernet destination, bytes 0-5, is not looked at, as in Linux.
+ *
+ * Reply r is the r-th eligible request in arrival order. It is written iff r < max_replies, with
+ * origin[r] the request's frame index, into the UDPDK_ARP_SLOT_BYTES slot at 64 r:
+ *   bytes 0-5    request bytes 22-27 (unicast to the asker)
+ *         6-11   cfg->src_mac
+ *         12-21  08 06 00 01 08 00 06 04 00 02
+ *         22-27  cfg->src_mac
+ *         28-31  cfg->src_ip
+ *         32-37  request bytes 22-27
+ *         38-41  request bytes 28-31
+ *         42-63  zero (a caller that wants a minimum-size Ethernet frame sends 60)
+ * Slots and origin entries of index >= replies are not written; the requests cut are a tail
+ * (no_room). cfg->dst_mac is not used.
+ *
+ * Asynchronous on the context stream; joins the pipes as udpdk_gpu_icmp_reply does. -EINVAL with
+ * nothing enqueued: a NULL pointer, cfg->src_ip == 0, frames_bytes >= 2^32, out->frames_dev not
+ * 16-byte aligned, an output that overlaps the frame buffer. n == 0 returns 0 with all counts zero.
+ * The frames buffer keeps the tailroom contract of udpdk_gpu_rx. meta and frames are read and never
+ * written. No snapshot is needed. The launch is not event-timed. One launch: its last workgroup to
+ * finish writes the replies, in time proportional to min(eligible, max_replies).
+ * ------------------------------------------------------------------------------------------- */
+#define UDPDK_ARP_FRAME_BYTES 42u   /* 14 Ethernet + 28 ARP; what is queued and sent            */
+#define UDPDK_ARP_SLOT_BYTES  64u   /* device output stride: the frame, then 22 zero bytes      */
+
+typedef struct {
+    uint8_t  *frames_dev;    /* [max_replies * 64], 16-byte aligned; reply r at 64 * r          */
+    uint32_t *origin_dev;    /* [max_replies] index of the request reply r answers              */
+    uint32_t  max_replies;
+} udpdk_arp_out_t;
+
+typedef struct {
+    uint32_t arp;         /* candidates past the frame gate with ethertype 0x0806               */
+    uint32_t malformed;   /* ... whose bytes 14-19 are not 00 01 08 00 06 04                    */
+    uint32_t other_op;    /* ... with an opcode other than 1 (replies to others, RARP, ...)     */
+    uint32_t own;         /* ... whose sender MAC is cfg->src_mac (our own frames coming back)  */
+    uint32_t sender_bad;  /* ... whose sender MAC has the group bit set or is all zero          */
+    uint32_t not_ours;    /* ... asking for another address                                     */
+    uint32_t conflict;    /* ... asking for ours while claiming it as sender (spa == our ip)    */
+    uint32_t eligible;    /* requests to answer                                                 */
+    uint32_t replies;     /* written: min(eligible, max_replies)                                */
+    uint32_t no_room;     /* eligible - replies (a tail in arrival order)                       */
+    uint32_t bad_frame;   /* candidate by meta, but length < 42 or out of range: not read       */
+} udpdk_arp_stats_t;
+
+int udpdk_gpu_arp_reply(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg,
+                        const udpdk_rx_batch_t *batch, const uint32_t *meta_dev,
+                        const udpdk_arp_out_t *out);
+/* Of the last udpdk_gpu_arp_reply on the context (-ENOENT when there was none). Synchronises.
+ * -ENOSPC when no_room > 0. */
+int udpdk_gpu_arp_stats(udpdk_gpu_ctx *ctx, udpdk_arp_stats_t *stats);
+/* Frames per workgroup of the kernel and the workgroup count for n frames (host only, like
+ * udpdk_gpu_icmp_geometry). */
+int udpdk_gpu_arp_geometry(uint32_t n, uint32_t *frames_per_block, uint32_t *n_blocks);
+/* Poller internals: the same stage on pipe `pipe`'s stream (1 .. 3) with that pipe's workspace and
+ * no joins, like udpdk_gpu_pipe_icmp_reply; the counts are copied to pinned memory on the same
+ * stream. udpdk_gpu_pipe_arp_stats reads them without synchronising: they are those of the pipe's
+ * last stage once udpdk_gpu_pipe_wait has returned (-ENOENT: the pipe never ran one; -ENOSPC as above). */
+int udpdk_gpu_pipe_arp_reply(udpdk_gpu_ctx *ctx, int pipe, const udpdk_tx_config_t *cfg,
+                             const udpdk_rx_batch_t *batch, const uint32_t *meta_dev,
+                             const udpdk_arp_out_t *out);
+int udpdk_gpu_pipe_arp_stats(udpdk_gpu_ctx *ctx, int pipe, udpdk_arp_stats_t *stats);
 
 /* ---------------------------------------------------------------------------------------------
  * Timing (for bench.py / the roofline): on every `enable`-th udpdk_gpu_rx call (0 = off, 1 =

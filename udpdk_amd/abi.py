@@ -208,6 +208,27 @@ class IcmpCounts(C.Structure):
                 ("limited", C.c_uint64), ("queue_dropped", C.c_uint64)]
 
 
+class ArpOut(C.Structure):
+    """udpdk_arp_out_t"""
+    _fields_ = [("frames_dev", C.c_void_p), ("origin_dev", C.c_void_p), ("max_replies", C.c_uint32)]
+
+
+ARP_STATS = ("arp", "malformed", "other_op", "own", "sender_bad", "not_ours", "conflict", "eligible", "replies",
+             "no_room", "bad_frame")
+ARP_FRAME_BYTES = 42
+ARP_SLOT_BYTES = 64
+
+
+class ArpStats(C.Structure):
+    """udpdk_arp_stats_t"""
+    _fields_ = [(k, C.c_uint32) for k in ARP_STATS]
+
+
+class ArpCounts(C.Structure):
+    """udpdk_arp_counts_t (udpdk_api.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("scanned",) + ARP_STATS[:-1] + ("announced",)]
+
+
 class IcmpErrStats(C.Structure):
     """udpdk_icmp_err_stats_t"""
     _fields_ = [("errors", C.c_uint32), ("msg_bad", C.c_uint32), ("quote_bad", C.c_uint32), ("soft", C.c_uint32),
@@ -308,6 +329,12 @@ _PROTOS = {
     "udpdk_gpu_pipe_icmp_errors": (C.c_int, [_P, C.c_int, C.c_uint32, C.POINTER(RxBatch), _P, _P, C.c_uint32, _P]),
     "udpdk_gpu_pipe_icmp_err_stats": (C.c_int, [_P, C.c_int, C.POINTER(IcmpErrStats)]),
     "udpdk_gpu_icmp_errno": (C.c_int, [C.c_uint32, C.POINTER(C.c_int)]),
+    "udpdk_gpu_arp_reply": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(RxBatch), _P, C.POINTER(ArpOut)]),
+    "udpdk_gpu_arp_stats": (C.c_int, [_P, C.POINTER(ArpStats)]),
+    "udpdk_gpu_arp_geometry": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_pipe_arp_reply": (C.c_int, [_P, C.c_int, C.POINTER(TxConfig), C.POINTER(RxBatch), _P,
+                                           C.POINTER(ArpOut)]),
+    "udpdk_gpu_pipe_arp_stats": (C.c_int, [_P, C.c_int, C.POINTER(ArpStats)]),
     "udpdk_gpu_timing_enable": (C.c_int, [_P, C.c_int]),
     "udpdk_gpu_timing_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "udpdk_gpu_rx_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
@@ -353,6 +380,9 @@ _PROTOS = {
     "udpdk_config_icmp_burst": (C.c_int, [C.c_int]),
     "udpdk_icmp_counts": (C.c_int, [C.POINTER(IcmpCounts)]),
     "udpdk_config_icmp_errors": (C.c_int, [C.c_int]),
+    "udpdk_config_arp": (C.c_int, [C.c_int]),
+    "udpdk_arp_announce": (C.c_int, []),
+    "udpdk_arp_counts": (C.c_int, [C.POINTER(ArpCounts)]),
     "udpdk_sock_error_post": (C.c_int, [C.c_int, C.c_uint32, C.c_uint16, C.c_uint32]),
     "udpdk_icmp_err_counts": (C.c_int, [C.POINTER(IcmpErrCounts)]),
     "udpdk_sock_rx_inject": (C.c_int, [C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint16]),
@@ -945,6 +975,49 @@ def icmp_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, meta, *, flags: i
             x.free()
 
 
+def arp_geometry(n: int) -> tuple[int, int]:
+    """(frames per workgroup, workgroups) of the ARP kernel for n frames."""
+    e = C.c_uint32()
+    k = C.c_uint32()
+    _check(lib().udpdk_gpu_arp_geometry(n, C.byref(e), C.byref(k)), "udpdk_gpu_arp_geometry")
+    return e.value, k.value
+
+
+def arp_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, meta, *, max_replies=None, n=None, pipe: int = 0,
+            pad: int = 8):
+    """udpdk_gpu_arp_reply (pipe 0) or udpdk_gpu_pipe_arp_reply + udpdk_gpu_pipe_wait over host verdict
+    words. Returns a dict: rc of the call, rc and dict of the stats call, meta as downloaded afterwards,
+    and slots [max_replies + pad, 64] and origin [max_replies + pad] as downloaded, `pad` elements longer
+    than the call may write and pre-filled with 0xA5 bytes."""
+    meta = np.ascontiguousarray(meta, np.uint32)
+    n = b.n if n is None else n
+    max_replies = n if max_replies is None else max_replies
+    bufs = [ctx.upload(meta if meta.size else np.zeros(1, np.uint32)),
+            ctx.upload(np.full(ARP_SLOT_BYTES * (max_replies + pad), 0xA5, np.uint8)),
+            ctx.upload(np.full(4 * (max_replies + pad), 0xA5, np.uint8))]
+    try:
+        bt = RxBatch(b.frames.ptr, b.frames_bytes, b.offset.ptr, b.length.ptr,
+                     b.ptype.ptr if b.ptype is not None else None, n)
+        o = ArpOut(bufs[1].ptr, bufs[2].ptr, max_replies)
+        st = ArpStats()
+        if pipe:
+            rc = lib().udpdk_gpu_pipe_arp_reply(ctx.handle, pipe, C.byref(cfg), C.byref(bt), C.c_void_p(bufs[0].ptr),
+                                                C.byref(o))
+            _check(lib().udpdk_gpu_pipe_wait(ctx.handle, pipe), "udpdk_gpu_pipe_wait")
+            src = lib().udpdk_gpu_pipe_arp_stats(ctx.handle, pipe, C.byref(st))
+        else:
+            rc = lib().udpdk_gpu_arp_reply(ctx.handle, C.byref(cfg), C.byref(bt), C.c_void_p(bufs[0].ptr), C.byref(o))
+            src = lib().udpdk_gpu_arp_stats(ctx.handle, C.byref(st))
+        ctx.sync()
+        return {"rc": rc, "stats_rc": src, "stats": {k: getattr(st, k) for k in ARP_STATS},
+                "meta": ctx.download(bufs[0], np.uint32, max(1, meta.size))[:meta.size],
+                "slots": ctx.download(bufs[1], np.uint8, ARP_SLOT_BYTES * (max_replies + pad)).reshape(-1, ARP_SLOT_BYTES),
+                "origin": ctx.download(bufs[2], np.uint32, max_replies + pad)}
+    finally:
+        for x in bufs:
+            x.free()
+
+
 def icmp_errno(code: int) -> tuple[int, int]:
     """udpdk_gpu_icmp_errno: (errno, hard) of a destination-unreachable code."""
     h = C.c_int(-1)
@@ -1236,6 +1309,19 @@ class HostApi:
     def icmp_err_counts(self) -> IcmpErrCounts:
         c = IcmpErrCounts()
         _check(self.L.udpdk_icmp_err_counts(C.byref(c)), "udpdk_icmp_err_counts")
+        return c
+
+    def config_arp(self, on: int) -> int:
+        """ARP replies from udpdk_poll_rx (udpdk_config_arp): returns the previous setting; a negative
+        `on` only reads it."""
+        return self.L.udpdk_config_arp(int(on))
+
+    def arp_announce(self) -> int:
+        return self.L.udpdk_arp_announce()
+
+    def arp_counts(self) -> ArpCounts:
+        c = ArpCounts()
+        _check(self.L.udpdk_arp_counts(C.byref(c)), "udpdk_arp_counts")
         return c
 
     def tx_pending(self) -> int:

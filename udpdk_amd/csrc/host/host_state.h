@@ -258,6 +258,13 @@ struct h_state {
     udpdk_icmp_counts_t icmp_counts;
     void     *ic_out_d, *ic_idx_d, *ic_h;
     uint64_t  ic_out_d_cap, ic_idx_d_cap, ic_h_cap;
+    /* ARP (rx_arp.c): [gpu] arp / udpdk_config_arp (0: a poll enqueues what it always did), the
+     * session's counts (under tx_lock; the replies and the announcement share the ICMP queue); work
+     * buffers of a fixed size: the device slots + origin, the pinned readback */
+    uint32_t  arp_on, arp_announce;
+    udpdk_arp_counts_t arp_counts;
+    void     *ar_out_d, *ar_h;
+    uint64_t  ar_out_d_cap, ar_h_cap;
     /* ICMP errors received (rx_icmp_err.c): [gpu] icmp_errors / udpdk_config_icmp_errors (0: a poll
      * enqueues what it always did), the session's counts (under lock) and the peer records the
      * contexts hold (h_peer_apply: what an error is posted against); work buffers, grow-only, one
@@ -336,6 +343,11 @@ uint32_t h_icmp_budget(void);
 int  h_icmp_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const uint32_t *meta_dev,
                   uint32_t *budget);
 
+
+/* rx_arp.c */
+void h_arp_reset(void);                   /* under tx_lock */
+void h_arp_buffers_free(void);
+int  h_arp_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const uint32_t *meta_dev, uint64_t not_ipv4);
 
 /* rx_icmp_err.c */
 void h_icmp_err_reset(void);              /* under g_udpdk.lock */

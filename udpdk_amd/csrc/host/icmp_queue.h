@@ -1,6 +1,7 @@
 /*
- * icmp_queue.h — the host queue of ICMP frames built by a poll and waiting for udpdk_tx_drain: a
- * bounded ring of at most H_ICMPQ_FRAMES frames whose bytes live in one ring of `cap` bytes. Every
+ * icmp_queue.h — the host queue of ICMP and ARP frames built by a poll (and of the ARP announcement)
+ * waiting for udpdk_tx_drain: a bounded ring of at most H_ICMPQ_FRAMES frames whose bytes live in one
+ * ring of `cap` bytes. Every
  * frame is contiguous (a frame that does not fit before the end of the byte ring starts at 0, as
  * long as the oldest frame leaves that much room). A frame that fits neither the frame ring nor the
  * byte ring is dropped and counted. Header-only and free of the library's state so that it can be

@@ -45,6 +45,8 @@ static void h_config_defaults(void)
     g_udpdk.icmp_flags = 0;            /* no ICMP answers, as in the reference */
     g_udpdk.icmp_burst = H_ICMP_BURST_DEFAULT;
     g_udpdk.icmp_errors = 0;           /* received ICMP errors are forgotten, as in the reference */
+    g_udpdk.arp_on = 0;                /* ARP requests are not answered, as in the reference */
+    g_udpdk.arp_announce = 0;
     g_udpdk.arena_bytes_max = 4ull << 30;
     g_udpdk.arena_count_max = 1024;
     g_udpdk.port_spec[0] = g_udpdk.port_peer[0] = 0;
@@ -74,6 +76,7 @@ void udpdk_host_reset(void)
     h_sockets_reset();
     h_icmp_reset();
     h_icmp_err_reset();
+    h_arp_reset();
     pthread_mutex_unlock(&g_udpdk.tx_lock);
     atomic_store(&g_udpdk.interrupted, 0);
     g_udpdk.snap_version = UINT64_MAX;
@@ -84,6 +87,7 @@ void udpdk_host_reset(void)
     g_udpdk.icmp_flags = 0;
     g_udpdk.icmp_burst = H_ICMP_BURST_DEFAULT;
     g_udpdk.icmp_errors = 0;
+    g_udpdk.arp_on = 0;
     pthread_mutex_unlock(&g_udpdk.lock);
 }
 
@@ -332,6 +336,15 @@ static int h_load_ini(const char *path)
              * 0 (default); checked against [gpu] devices once the file is read */
             if (!strcmp(v, "0") || !strcmp(v, "1")) g_udpdk.icmp_errors = (uint32_t)(v[0] - '0');
             else { rc = -1; break; }
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "arp")) {
+            /* 1: a poll answers ARP requests for our address on the GPU (udpdk_gpu_arp_reply);
+             * 0 (default); checked against [gpu] devices once the file is read */
+            if (!strcmp(v, "0") || !strcmp(v, "1")) g_udpdk.arp_on = (uint32_t)(v[0] - '0');
+            else { rc = -1; break; }
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "arp_announce")) {
+            /* 1: udpdk_init queues one RFC 5227 announcement of our address (udpdk_arp_announce) */
+            if (!strcmp(v, "0") || !strcmp(v, "1")) g_udpdk.arp_announce = (uint32_t)(v[0] - '0');
+            else { rc = -1; break; }
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port")) {
             snprintf(g_udpdk.port_spec, sizeof(g_udpdk.port_spec), "%s", v);
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port_peer")) {
@@ -348,6 +361,8 @@ static int h_load_ini(const char *path)
     if (!rc && g_udpdk.icmp_flags && g_udpdk.n_shards > 1) rc = -1;
     /* ... and do not report received errors (udpdk_config_icmp_errors: ENOTSUP, here as -2) */
     if (!rc && g_udpdk.icmp_errors && g_udpdk.n_shards > 1) rc = -2;
+    /* ... and do not answer ARP (udpdk_config_arp: ENOTSUP; here EINVAL, as for [gpu] icmp) */
+    if (!rc && g_udpdk.arp_on && g_udpdk.n_shards > 1) rc = -1;
     return rc;
 }
 
@@ -396,6 +411,13 @@ int udpdk_init(int argc, char *argv[])
         g_udpdk.n_shards = 0;
     }
     g_udpdk.snap_version = UINT64_MAX;
+    /* [gpu] arp_announce: queued before the poller starts, so its first drain sends it */
+    if (g_udpdk.arp_announce && udpdk_arp_announce()) {
+        const int e = errno;
+        udpdk_cleanup();
+        errno = e;
+        return -1;
+    }
     /* [gpu] port: start the poller thread on it now, as the reference forks its poller here
      * (udpdk_init.c:293, :362-368), so an unmodified application's sendto / recvfrom move
      * packets without further calls */
@@ -455,6 +477,7 @@ void udpdk_cleanup(void)
     h_echo_buffers_free();
     h_icmp_buffers_free();
     h_icmp_err_buffers_free();
+    h_arp_buffers_free();
     h_arenas_free_all();
     g_udpdk.frag_ready = 0;
     h_shards_destroy();

@@ -1234,6 +1234,11 @@ static int h_poll_chunked(const uint8_t *frames, uint64_t frames_bytes, const ui
         if ((rc = udpdk_gpu_pipe_batch(g, h_pipe_of(k), &staged, &meta_dev))) { err = -rc; break; }
         uint32_t nd = 0;
         const uint64_t nfrag = C->st.counters[UDPDK_V_FRAG];
+        /* [gpu] arp: the chunk's ARP replies, on its pipe, queued ahead of its ICMP answers */
+        if (h_arp_stage(g, h_pipe_of(k), &staged, meta_dev, C->st.counters[UDPDK_C_VERDICT0 + UDPDK_V_NOT_IPV4])) {
+            err = errno;
+            break;
+        }
         /* [gpu] icmp: the chunk's answers, on its pipe, before reassembly touches the frames */
         if (h_icmp_stage(g, h_pipe_of(k), &staged, meta_dev, &icmp_budget)) { err = errno; break; }
         /* [gpu] icmp_errors: the chunk's ICMP errors for connected sockets, on its pipe */
@@ -1373,6 +1378,9 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
             goto out;
         for (uint32_t d = 0; d < nd; d++) g_udpdk.fr_org[d] = g_udpdk.fb_idx[g_udpdk.fr_org[d]];
     } else if (!sharded) {
+        /* [gpu] arp: replies to the staged batch's requests for our address, queued ahead of its ICMP
+         * answers (nothing is enqueued with the switch off or for a batch of pure IPv4) */
+        if (h_arp_stage(g, 0, &staged, meta_dev, st.counters[UDPDK_C_VERDICT0 + UDPDK_V_NOT_IPV4])) goto out;
         /* [gpu] icmp: echo replies and port-unreachable errors for the staged batch, queued for
          * udpdk_tx_drain, before reassembly touches the frames (nothing is enqueued with flags 0) */
         uint32_t icmp_budget = h_icmp_budget();

@@ -10,8 +10,8 @@
  * payload copy, fragmentation at the MTU, the UDP checksum with [gpu] tx_udp_cksum = 1) and one
  * D2H returns them.
  *
- * ICMP frames a poll built (rx_icmp.c) leave first, oldest first, copied from their host queue; the
- * socket datagrams follow in what room is left. A queued ICMP frame that does not fit the caller's
+ * ARP and ICMP frames a poll built (rx_arp.c, rx_icmp.c) and the ARP announcement leave first, oldest
+ * first, copied from their host queue; the socket datagrams follow in what room is left. A queued frame that does not fit the caller's
  * limits stays queued, and the datagrams wait behind it for the next drain.
  */
 #include <errno.h>
@@ -70,7 +70,7 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
     pthread_mutex_lock(&g_udpdk.tx_lock);
     pthread_mutex_unlock(&g_udpdk.lock);
     int ret = -1, rc;
-    /* 0. the queued ICMP frames */
+    /* 0. the queued ARP and ICMP frames */
     uint32_t k0 = 0;
     uint64_t b0 = 0;
     h_icmpq_drain(&g_udpdk.icmpq, out, out_cap, out_off, out_len, max, &k0, &b0);

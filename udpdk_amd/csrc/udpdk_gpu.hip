@@ -24,6 +24,7 @@
 #include "rx_peer.h"
 #include "icmp_reply.h"
 #include "icmp_error.h"
+#include "arp_reply.h"
 #include "rss_host.h"
 
 using namespace udpdk;
@@ -169,6 +170,16 @@ struct IcmpWs {
 // (udpdk_gpu_icmp_errors) and one per pipe (udpdk_gpu_pipe_icmp_errors).
 using IcmpErrWs = ResultSlot<IcmpErrResult>;
 
+// Workspace of the ARP reply stage (arp_reply.hip), lazily sized by the context's max_frames: one for
+// the context stream (udpdk_gpu_arp_reply) and one per pipe (udpdk_gpu_pipe_arp_reply).
+struct ArpWs {
+    DevBuf<ArpEntry> cand;
+    DevBuf<uint32_t> row;                      // the rows, then rbase
+    DevBuf<unsigned long long> fuse;           // fan-in words, zeroed once: every launch leaves zeros
+    ResultSlot<ArpResult> res;
+    void release() { release_all(cand, row, fuse, res); }
+};
+
 // The sticky lane-removal stages, in the order rx_on_pipe applies them.
 enum { ST_DROP, ST_BALANCE, ST_PEER, N_STICKY };
 
@@ -209,10 +220,11 @@ struct Pipe {
     const uint32_t *staged_meta = nullptr;    // and its verdict words
     IcmpWs icmp;                              // udpdk_gpu_pipe_icmp_reply on this pipe's stream
     IcmpErrWs icmp_err;                       // udpdk_gpu_pipe_icmp_errors on this pipe's stream
+    ArpWs arp;                                // udpdk_gpu_pipe_arp_reply on this pipe's stream
     void release()
     {
         release_all(hist, partial, base, agg, ticket, fuse, tile_cnt, res, flt, bal, peer, st_frames_d,
-                    st_desc_d, st_out_d, st_frames_h, st_desc_h, icmp, icmp_err);
+                    st_desc_d, st_out_d, st_frames_h, st_desc_h, icmp, icmp_err, arp);
     }
 };
 constexpr int MAX_PIPES = 4;
@@ -275,6 +287,7 @@ struct udpdk_gpu_ctx {
     ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
     IcmpWs icmp;                              // udpdk_gpu_icmp_reply (the context stream)
     IcmpErrWs icmp_err;                       // udpdk_gpu_icmp_errors (the context stream)
+    ArpWs arp;                                // udpdk_gpu_arp_reply (the context stream)
 
     unsigned long long *dbg = nullptr;        // diagnostic stamp buffer (UDPDK_STAMPS builds)
     Reasm *reasm = nullptr;                   // udpdk_gpu_frag_table_create
@@ -302,7 +315,7 @@ struct udpdk_gpu_ctx {
     {
         for (Pipe &P : pipes) P.release();
         release_all(port_tab, binds, slots, hint, xflt, bal_rp, bal_ktab, xbal, peer_tab, xpeer, rpl, icmp,
-                    icmp_err, rss_reta, rss_ktab, rss_qid, rss_hist, rss_partial, rss_total, rss_fuse);
+                    icmp_err, arp, rss_reta, rss_ktab, rss_qid, rss_hist, rss_partial, rss_total, rss_fuse);
     }
 };
 
@@ -2288,6 +2301,137 @@ int udpdk_gpu_icmp_errno(uint32_t code, int *hard)
                                 EHOSTUNREACH, EHOSTUNREACH, EHOSTUNREACH, EHOSTUNREACH};
     if (hard) *hard = code < 16u ? (int)((ICMP_ERR_HARD_MASK >> code) & 1u) : 0;
     return code < 16u ? err[code] : 0;
+}
+
+namespace {
+
+// Argument checks of udpdk_gpu_arp_reply and its pipe form: nothing is enqueued unless all pass.
+int arp_check(const udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
+              const uint32_t *meta_dev, const udpdk_arp_out_t *o)
+{
+    if (!c || !cfg || !bt || !meta_dev || !o) return -EINVAL;
+    if (cfg->src_ip == 0u) return -EINVAL;
+    if (bt->frames_bytes >= (1ull << 32)) return -EINVAL;
+    if (!o->frames_dev || !o->origin_dev) return -EINVAL;
+    if ((uintptr_t)o->frames_dev & 15u) return -EINVAL;
+    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
+    if (bt->frames_dev) {
+        // the frame buffer with its tailroom against the slots and the origin entries
+        const uintptr_t f0 = (uintptr_t)bt->frames_dev, f1 = f0 + bt->frames_bytes + UDPDK_GPU_FRAMES_TAILROOM;
+        const uintptr_t o0 = (uintptr_t)o->frames_dev, o1 = o0 + (uint64_t)o->max_replies * ARP_SLOT;
+        const uintptr_t g0 = (uintptr_t)o->origin_dev, g1 = g0 + (uint64_t)o->max_replies * 4u;
+        if ((o0 < f1 && f0 < o1) || (g0 < f1 && f0 < g1)) return -EINVAL;
+    }
+    return 0;
+}
+
+// The stage (arp_reply.hip) on stream st with workspace W: one launch.
+int arp_enqueue(udpdk_gpu_ctx *c, ArpWs &W, hipStream_t st, const udpdk_tx_config_t *cfg,
+                const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, const udpdk_arp_out_t *o)
+{
+    const uint32_t nb = ceil_div(bt->n, ARP_TILE);
+    const size_t rows = std::max<size_t>(ceil_div(std::max(bt->n, c->max_frames), ARP_TILE), 1);
+    int rc;
+    if ((rc = W.cand.ensure(c, rows * ARP_TILE)) || (rc = W.row.ensure(c, rows * (ARP_ROW + 1))) ||
+        (rc = W.res.ensure(c)))
+        return rc;
+    if (!W.fuse) {
+        if ((rc = W.fuse.ensure(c, FUSE_BYTES / 8))) return rc;
+        HIPC(c, hipMemsetAsync(W.fuse, 0, FUSE_BYTES, st));
+    }
+    if (!bt->n) {
+        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(ArpResult), st));
+        W.res.ran = true;
+        return 0;
+    }
+    ArpArgs aa;
+    aa.frames = bt->frames_dev;
+    aa.offset = bt->offset_dev;
+    aa.length = bt->length_dev;
+    aa.meta = meta_dev;
+    aa.out = o->frames_dev;
+    aa.origin = o->origin_dev;
+    aa.cand = W.cand;
+    aa.row = W.row;
+    aa.rbase = W.row + (size_t)ARP_ROW * nb;
+    aa.fuse = W.fuse;
+    aa.res = W.res.dev;
+    aa.n = bt->n;
+    aa.n_blocks = nb;
+    aa.frames_bytes = (uint32_t)bt->frames_bytes;
+    aa.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+    aa.max_replies = o->max_replies;
+    aa.src_ip = cfg->src_ip;
+    aa.mac_lo = aa.mac_hi = 0u;
+    memcpy(&aa.mac_lo, cfg->src_mac, 4);
+    memcpy(&aa.mac_hi, cfg->src_mac + 4, 2);
+    hipLaunchKernelGGL(arp_reply, dim3(nb), dim3(ARP_BLOCK), 0, st, aa);
+    HIPC(c, hipGetLastError());
+    W.res.ran = true;
+    return 0;
+}
+
+int arp_stats_out(const ArpResult *r, udpdk_arp_stats_t *st)
+{
+    st->arp = r->c[ARP_R_ARP];
+    st->malformed = r->c[ARP_R_MALFORMED];
+    st->other_op = r->c[ARP_R_OTHER_OP];
+    st->own = r->c[ARP_R_OWN];
+    st->sender_bad = r->c[ARP_R_SENDER_BAD];
+    st->not_ours = r->c[ARP_R_NOT_OURS];
+    st->conflict = r->c[ARP_R_CONFLICT];
+    st->eligible = r->c[ARP_R_ELIGIBLE];
+    st->replies = r->replies;
+    st->no_room = r->no_room;
+    st->bad_frame = r->c[ARP_R_BAD_FRAME];
+    return st->no_room ? -ENOSPC : 0;
+}
+
+} // namespace
+
+int udpdk_gpu_arp_geometry(uint32_t n, uint32_t *frames_per_block, uint32_t *n_blocks)
+{
+    if (!frames_per_block || !n_blocks) return -EINVAL;
+    *frames_per_block = ARP_TILE;
+    *n_blocks = std::max<uint32_t>(1u, ceil_div(n, ARP_TILE));
+    return 0;
+}
+
+int udpdk_gpu_arp_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
+                        const uint32_t *meta_dev, const udpdk_arp_out_t *o)
+{
+    int rc = arp_check(c, cfg, bt, meta_dev, o);
+    if (rc) return rc;
+    if ((rc = on_ctx_stream(c))) return rc;
+    return arp_enqueue(c, c->arp, c->stream, cfg, bt, meta_dev, o);
+}
+
+int udpdk_gpu_arp_stats(udpdk_gpu_ctx *c, udpdk_arp_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    const int rc = ctx_result(c, c->arp.res);
+    return rc ? rc : arp_stats_out(c->arp.res.host, st);
+}
+
+int udpdk_gpu_pipe_arp_reply(udpdk_gpu_ctx *c, int pipe, const udpdk_tx_config_t *cfg,
+                             const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, const udpdk_arp_out_t *o)
+{
+    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    int rc = arp_check(c, cfg, bt, meta_dev, o);
+    if (rc) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    Pipe &P = c->pipes[pipe];
+    P.dirty = true;
+    if ((rc = arp_enqueue(c, P.arp, P.stream, cfg, bt, meta_dev, o))) return rc;
+    // the counts follow on the pipe's stream: udpdk_gpu_pipe_arp_stats reads them after udpdk_gpu_pipe_wait
+    return P.arp.res.enqueue_fetch(c, P.stream);
+}
+
+int udpdk_gpu_pipe_arp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_arp_stats_t *st)
+{
+    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    const ResultSlot<ArpResult> &R = c->pipes[pipe].arp.res;
+    return R.ran ? arp_stats_out(R.host, st) : -ENOENT;
 }
 
 #ifdef UDPDK_STAMPS
