@@ -358,8 +358,8 @@ int udpdk_icmp_err_counts(udpdk_icmp_err_counts_t *counts);
  * answer: there on = 1 gives -1 with ENOTSUP and udpdk_init fails on such an ini, as for
  * udpdk_config_icmp. With no source address configured nothing is answered. With the loopback port our
  * own replies come back as other_op and our announcement as own: nothing is answered twice. Not done:
- * a neighbour cache, sending requests, resolving the destination MAC of what we send (still the
- * configured [port0_dst] MAC), defending our address, VLAN tags. Returns the value in force before
+ * defending our address, VLAN tags (the neighbour cache, requests and per-destination MACs are
+ * udpdk_config_neigh's). Returns the value in force before
  * the call; a negative argument only reads it; above 1: -1, EINVAL. */
 int udpdk_config_arp(int on);
 /* Queue one RFC 5227 announcement of our address (a broadcast request with sender and target address
@@ -375,6 +375,47 @@ typedef struct {
              announced;
 } udpdk_arp_counts_t;
 int udpdk_arp_counts(udpdk_arp_counts_t *counts);
+
+/* Neighbours (ini: [gpu] neigh = 0 | 1 | fallback; default 0: as in the reference, every frame goes to
+ * the [port0_dst] MAC). With the switch on the main context keeps a neighbour table (udpdk_gpu.h; ini:
+ * [gpu] neigh_entries, default 1024; neigh_ttl_ms, default 30000; neigh_retrans_ms, default 1000), and
+ *  - udpdk_poll_rx runs udpdk_gpu_neigh_learn on every staged batch whose RX counters show a frame that
+ *    is not IPv4, behind the ARP replies and on the same pipe: the stack learns from the ARP it
+ *    receives (requests for its address, and replies and announcements about what it asked for). This
+ *    does not need [gpu] arp = 1. Time is the monotonic clock in milliseconds;
+ *  - udpdk_tx_drain resolves every datagram before the build (udpdk_gpu_neigh_resolve, rules R1-R5,
+ *    with ini [port0] netmask, default 0: everything is on-link, and [port0] gateway) and
+ *    udpdk_gpu_tx_build_neigh writes its next hop's MAC into its frames. The who-has requests for what
+ *    is not known (at most 256 a drain) go onto the host queue of the ARP and ICMP frames and leave
+ *    first in the next drain. A datagram without a MAC is, in mode 1 (strict), dequeued, dropped and
+ *    counted (tx_unresolved; its span in the drain's output is a gap), as the drain drops what it
+ *    cannot send; in mode 2 (fallback) it goes to the [port0_dst] MAC while the request is out. A
+ *    destination without a route is dropped in both. In strict mode [port0_dst] is not needed.
+ * Off, a poll and a drain call what they always called. Not done: the ICMP answers and udpdk_poll_echo
+ * keep the configured MAC; no hold queue for unresolved datagrams; expired entries are not removed from
+ * a full table; nothing is learned from IPv4 traffic; no address defence; sharded polls (there a mode
+ * above 0 gives -1 with ENOTSUP and udpdk_init fails on such an ini, as for udpdk_config_arp).
+ * Returns the mode in force before the call; a negative argument only reads it; above 2: -1, EINVAL. */
+#define UDPDK_NEIGH_MODE_OFF      0
+#define UDPDK_NEIGH_MODE_STRICT   1
+#define UDPDK_NEIGH_MODE_FALLBACK 2
+int udpdk_config_neigh(int mode);
+/* A static entry (never learned over, never expires) for raw address ip. Needs the session's GPU
+ * (ENODEV); -1 with ENOSPC when the table is full, EINVAL for address 0. udpdk_neigh_flush clears the
+ * table, static entries included. */
+int udpdk_neigh_add(uint32_t ip, const uint8_t mac[6]);
+int udpdk_neigh_flush(void);
+/* Session sums over polls and drains: the learn stage's counts (udpdk_neigh_learn_stats_t), the resolve
+ * stage's (udpdk_neigh_resolve_stats_t, its `requests` aside), the datagrams a drain dropped for want
+ * of a MAC or a route (tx_unresolved) and the who-has frames queued (requests). udpdk_host_reset zeroes
+ * them. */
+typedef struct {
+    uint64_t arp, malformed, bad_frame, other_op, sender_bad, updated, refreshed, static_kept, created, full, ignored;
+    uint64_t skipped, bcast, mcast, no_route, self, hit, expired, incomplete, inserted, table_full, fallback,
+             unresolved, no_room;
+    uint64_t tx_unresolved, requests;
+} udpdk_neigh_counts_t;
+int udpdk_neigh_counts(udpdk_neigh_counts_t *counts);
 
 /* Socket slot state (exch_slot_info, udpdk_types.h:40-47) for the GPU TX slot table. */
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots);

@@ -57,7 +57,10 @@ extern "C" {
  *    (still 3: udpdk_gpu_icmp_errors / udpdk_gpu_icmp_err_stats / udpdk_gpu_pipe_icmp_errors /
  *    udpdk_gpu_pipe_icmp_err_stats / udpdk_gpu_icmp_errno were added)
  *    (still 3: udpdk_gpu_arp_reply / udpdk_gpu_arp_stats / udpdk_gpu_arp_geometry /
- *    udpdk_gpu_pipe_arp_reply / udpdk_gpu_pipe_arp_stats were added) */
+ *    udpdk_gpu_pipe_arp_reply / udpdk_gpu_pipe_arp_stats were added)
+ *    (still 3: udpdk_gpu_neigh_create / _set / _dump / _flush / _learn / _learn_stats / _resolve /
+ *    _resolve_stats / _geometry / _class, udpdk_gpu_pipe_neigh_learn / _learn_stats and
+ *    udpdk_gpu_tx_build_neigh were added) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -1029,6 +1032,166 @@ int udpdk_gpu_pipe_arp_reply(udpdk_gpu_ctx *ctx, int pipe, const udpdk_tx_config
                              const udpdk_rx_batch_t *batch, const uint32_t *meta_dev,
                              const udpdk_arp_out_t *out);
 int udpdk_gpu_pipe_arp_stats(udpdk_gpu_ctx *ctx, int pipe, udpdk_arp_stats_t *stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * Neighbour cache on the device: a table of on-link IPv4 addresses and their MACs, learned from the
+ * ARP the stack receives (udpdk_gpu_neigh_learn, after udpdk_gpu_rx) and read per datagram before
+ * udpdk_gpu_tx_build_neigh (udpdk_gpu_neigh_resolve), which also writes the who-has requests for
+ * what it does not know. The reference has none: every frame goes to the one MAC of its .ini. Off
+ * unless called. All addresses are raw.
+ *
+ * The table: open addressing keyed by the address, 16-byte entries, a power of two of them in
+ * 8 .. UDPDK_NEIGH_MAX_ENTRIES. Key 0 is an empty slot (0.0.0.0 is never a neighbour). Kernels never
+ * delete: an entry only changes state in place, so a key, once claimed, stays where it is. Probing is
+ * linear over the whole table from the key's home slot, (key * 0x9E3779B1 mod 2^32) >> (32 - log2
+ * entries), so an insert fails only when no slot is empty. Time is the caller's `now` in milliseconds;
+ * ages are now - stamp in uint32 arithmetic (wrap-safe); nothing reads a clock. The table has ONE
+ * writer at a time: learn, resolve, set and flush are ordered by the caller (the stream forms are
+ * ordered by their stream, and join the pipes as udpdk_gpu_tx_build does). Its contents as a map
+ * (address -> MAC, state, stamp) are fully determined by the calls; its layout is not, with one
+ * exception: when one call brings more new keys than there are empty slots, which of them got in is
+ * unspecified (how many is specified).
+ *
+ * Learning (udpdk_gpu_neigh_learn). Candidates and the frame gate are those of udpdk_gpu_arp_reply,
+ * steps 1-4 (verdict UDPDK_V_NOT_IPV4; length >= 42 and in range, else bad_frame; bytes 12-13 08 06,
+ * then arp++; bytes 14-19 00 01 08 00 06 04, else malformed). Then:
+ *   5. Opcode, bytes 20-21, 1 or 2, else other_op.
+ *   6. sender_bad: the sender MAC, bytes 22-27, is cfg->src_mac, has the group bit or is all zero;
+ *      or the sender address, bytes 28-31, is 0.0.0.0, cfg->src_ip, 255.255.255.255 or in 224/4.
+ *   7. The table has an entry for the sender address: a STATIC one is never touched (static_kept);
+ *      any other becomes REACHABLE with the sender's MAC and stamp = now, counted updated when its
+ *      MAC or state changed and refreshed otherwise.
+ *   8. No entry, and the frame is a request (opcode 1) whose target address, bytes 38-41, is
+ *      cfg->src_ip: a REACHABLE entry is created (created), or there is no empty slot (full).
+ *   9. Otherwise nothing is learned (ignored): replies and gratuitous ARP about addresses the stack
+ *      never asked for, requests for others. This is Linux with arp_accept = 0 (RFC 826 would create
+ *      from any packet addressed to us). A solicited reply finds the INCOMPLETE entry resolve left.
+ * Frames are taken in frame order: the last frame of an address wins, and every count is taken
+ * against the table as the frames before it left it. meta and frames are read and never written.
+ * Asynchronous; -EINVAL with nothing enqueued: a NULL pointer, no table, cfg->src_ip == 0, unknown
+ * flag bits, frames_bytes >= 2^32. n == 0 returns 0 with all counts zero. One launch of
+ * arp_reply's shape; its last workgroup to finish applies the events, one workgroup's width at a time,
+ * so a batch without ARP costs the read of meta.
+ *
+ * Resolution (udpdk_gpu_neigh_resolve) of datagram i from dst_ip[i] and sockfd[i]; a negative sockfd
+ * passes through (skipped, MAC zero). In order:
+ *   R1. dst = 255.255.255.255, or netmask != 0 and dst on-link with all host bits one:
+ *       ff:ff:ff:ff:ff:ff (bcast).
+ *   R2. dst in 224/4: 01:00:5e + the low 23 bits of dst (mcast).
+ *   R3. The next hop h = dst when (dst ^ src_ip) & netmask == 0 (netmask 0: everything is on-link),
+ *       else gateway. h == 0 (off-link without a gateway): no_route, sockfd_out = -1, no request.
+ *   R4. h == src_ip: src_mac (self).
+ *   R5. The entry of h: STATIC, or REACHABLE with now - stamp <= ttl_ms: its MAC (hit). REACHABLE and
+ *       older: it becomes INCOMPLETE with stamp = now (expired; a miss that asks). INCOMPLETE
+ *       (incomplete): a miss, which asks iff now - stamp >= retrans_ms, and then stamp = now
+ *       (retrans_ms 0 is taken as 1: a next hop is asked at most once per call). None: an INCOMPLETE
+ *       entry with stamp = now is inserted (inserted; a miss that asks), or no slot is empty
+ *       (table_full; a miss that does not ask).
+ *   A miss gets cfg->fallback_mac and keeps its sockfd with UDPDK_NEIGH_FALLBACK (fallback), else MAC
+ *   zero and sockfd_out = -1 (unresolved): udpdk_gpu_tx_build_neigh writes nothing for it.
+ * Datagrams are taken in index order: states and stamps afterwards and the requests are those of a
+ * serial walk. state[i] is the UDPDK_NEIGH_C_* class. dmac[2 i], dmac[2 i + 1] hold the MAC in their
+ * low 48 bits (bytes 0-3, then 4-5). Request r, for the r-th distinct asking next hop in the order of
+ * the first datagram that asked (req_origin[r]), is written iff r < req_cap into the
+ * UDPDK_ARP_SLOT_BYTES slot at 64 r:
+ *   bytes 0-5 ff, 6-11 src_mac, 12-21 08 06 00 01 08 00 06 04 00 01, 22-27 src_mac, 28-31 src_ip,
+ *   32-37 zero, 38-41 h, 42-63 zero.
+ * The excess counts as no_room; stamps move for every asking next hop, whether its request fitted or
+ * not. Nothing is written at or past the request count. dst_ip and sockfd are never written.
+ * -EINVAL with nothing enqueued: a NULL pointer (req_dev and req_origin_dev may be NULL when req_cap
+ * is 0), no table, src_ip == 0, unknown flag bits, dmac_dev not 8-byte or req_dev not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define UDPDK_NEIGH_MAX_ENTRIES 65536u
+#define UDPDK_NEIGH_FALLBACK    1u      /* udpdk_neigh_cfg_t::flags: a miss goes to fallback_mac   */
+
+enum udpdk_neigh_state {
+    UDPDK_NEIGH_EMPTY = 0, UDPDK_NEIGH_INCOMPLETE = 1, UDPDK_NEIGH_REACHABLE = 2, UDPDK_NEIGH_STATIC = 3
+};
+
+/* the class of a datagram (udpdk_neigh_out_t::state_dev, udpdk_gpu_neigh_class) */
+enum udpdk_neigh_class {
+    UDPDK_NEIGH_C_SKIPPED = 0, UDPDK_NEIGH_C_BCAST = 1, UDPDK_NEIGH_C_MCAST = 2, UDPDK_NEIGH_C_NO_ROUTE = 3,
+    UDPDK_NEIGH_C_SELF = 4,
+    UDPDK_NEIGH_C_LOOKUP = 5,           /* udpdk_gpu_neigh_class only: rule R5 decides             */
+    UDPDK_NEIGH_C_HIT = 5, UDPDK_NEIGH_C_EXPIRED = 6, UDPDK_NEIGH_C_INCOMPLETE = 7, UDPDK_NEIGH_C_INSERTED = 8,
+    UDPDK_NEIGH_C_TABLE_FULL = 9
+};
+
+typedef struct {
+    uint32_t ip;          /* raw; 0: an empty slot                                                  */
+    uint8_t  mac[6];
+    uint8_t  state;       /* enum udpdk_neigh_state                                                 */
+    uint8_t  pad;
+    uint32_t stamp;       /* ms: when it was learned (REACHABLE) or last asked for (INCOMPLETE)     */
+} udpdk_neigh_entry_t;
+
+typedef struct {
+    uint32_t src_ip, netmask, gateway;   /* raw; netmask 0: all on-link; gateway 0: none           */
+    uint8_t  src_mac[6];
+    uint8_t  fallback_mac[6];
+    uint32_t ttl_ms;                     /* a REACHABLE entry is used while now - stamp <= ttl_ms   */
+    uint32_t retrans_ms;                 /* an INCOMPLETE one is asked for again after this long    */
+    uint32_t flags;                      /* UDPDK_NEIGH_FALLBACK                                    */
+} udpdk_neigh_cfg_t;
+
+typedef struct {
+    uint32_t arp, malformed, bad_frame;  /* as in udpdk_arp_stats_t                                 */
+    uint32_t other_op;                   /* an opcode other than 1 and 2                            */
+    uint32_t sender_bad, updated, refreshed, static_kept, created, full, ignored;   /* steps 6-9   */
+} udpdk_neigh_learn_stats_t;
+
+typedef struct {
+    uint32_t *dmac_dev;        /* [2 n], 8-byte aligned                                             */
+    int32_t  *sockfd_out_dev;  /* [n]                                                               */
+    uint8_t  *state_dev;       /* [n] enum udpdk_neigh_class                                        */
+    uint8_t  *req_dev;         /* [req_cap * 64], 16-byte aligned                                   */
+    uint32_t *req_origin_dev;  /* [req_cap]                                                         */
+    uint32_t  req_cap;
+} udpdk_neigh_out_t;
+
+typedef struct {
+    uint32_t skipped, bcast, mcast, no_route, self, hit;          /* one per datagram, with ...     */
+    uint32_t expired, incomplete, inserted, table_full;           /* ... these, the misses          */
+    uint32_t fallback, unresolved;                                /* what became of the misses      */
+    uint32_t requests, no_room;                                   /* written, and cut               */
+} udpdk_neigh_resolve_stats_t;
+
+/* Allocates and clears a table of `entries`, replacing an existing one (freed with the context).
+ * Synchronises. -EINVAL: entries not a power of two in 8 .. UDPDK_NEIGH_MAX_ENTRIES. */
+int udpdk_gpu_neigh_create(udpdk_gpu_ctx *ctx, uint32_t entries);
+/* Inserts or overwrites n entries (STATIC or REACHABLE, ip != 0) from the host. Synchronous.
+ * -ENOSPC when the table is full: the entries before the one that did not fit are in. */
+int udpdk_gpu_neigh_set(udpdk_gpu_ctx *ctx, const udpdk_neigh_entry_t *entries_host, uint32_t n);
+/* The non-empty entries, up to cap of them, in the table's order (callers sort); *n gets their
+ * number (-ENOSPC when it is above cap). Synchronous. */
+int udpdk_gpu_neigh_dump(udpdk_gpu_ctx *ctx, udpdk_neigh_entry_t *out_host, uint32_t cap, uint32_t *n);
+/* Clears the table; keep_static != 0 keeps the STATIC entries. Synchronous. */
+int udpdk_gpu_neigh_flush(udpdk_gpu_ctx *ctx, int keep_static);
+int udpdk_gpu_neigh_learn(udpdk_gpu_ctx *ctx, const udpdk_neigh_cfg_t *cfg, const udpdk_rx_batch_t *batch,
+                          const uint32_t *meta_dev, uint32_t now);
+/* Of the last udpdk_gpu_neigh_learn on the context (-ENOENT when there was none). Synchronises. */
+int udpdk_gpu_neigh_learn_stats(udpdk_gpu_ctx *ctx, udpdk_neigh_learn_stats_t *stats);
+/* Poller internals: the same stage on pipe `pipe`'s stream (1 .. 3), as udpdk_gpu_pipe_arp_reply is. */
+int udpdk_gpu_pipe_neigh_learn(udpdk_gpu_ctx *ctx, int pipe, const udpdk_neigh_cfg_t *cfg,
+                               const udpdk_rx_batch_t *batch, const uint32_t *meta_dev, uint32_t now);
+int udpdk_gpu_pipe_neigh_learn_stats(udpdk_gpu_ctx *ctx, int pipe, udpdk_neigh_learn_stats_t *stats);
+int udpdk_gpu_neigh_resolve(udpdk_gpu_ctx *ctx, const udpdk_neigh_cfg_t *cfg, const uint32_t *dst_ip_dev,
+                            const int32_t *sockfd_dev, uint32_t n, uint32_t now, const udpdk_neigh_out_t *out);
+/* Of the last udpdk_gpu_neigh_resolve (-ENOENT when there was none; -ENOSPC when no_room > 0).
+ * Synchronises. */
+int udpdk_gpu_neigh_resolve_stats(udpdk_gpu_ctx *ctx, udpdk_neigh_resolve_stats_t *stats);
+/* Frames per workgroup of the learn kernel and datagrams per workgroup of the resolve kernel (host
+ * only, like udpdk_gpu_arp_geometry). */
+int udpdk_gpu_neigh_geometry(uint32_t *learn_frames_per_block, uint32_t *resolve_per_block);
+/* Rules R1-R4 on the host, the statement the kernel compiles too: returns the class of dst_ip
+ * (UDPDK_NEIGH_C_BCAST, _MCAST, _NO_ROUTE, _SELF or _LOOKUP), with *next_hop (0 where the class has
+ * none) and, for bcast, mcast and self, the MAC in mac_out[6] (zero otherwise). -EINVAL: a NULL pointer. */
+int udpdk_gpu_neigh_class(const udpdk_neigh_cfg_t *cfg, uint32_t dst_ip, uint32_t *next_hop, uint8_t *mac_out);
+/* udpdk_gpu_tx_build_flags with bytes 0-5 of every frame (every fragment) of datagram i taken from
+ * dmac_dev[2 i], dmac_dev[2 i + 1] (udpdk_neigh_out_t::dmac_dev) instead of cfg->dst_mac; every other
+ * byte is the same. dmac_dev == NULL is udpdk_gpu_tx_build_flags exactly. */
+int udpdk_gpu_tx_build_neigh(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg, const udpdk_tx_batch_t *batch,
+                             const udpdk_tx_out_t *out, uint32_t mtu, uint32_t flags, const uint32_t *dmac_dev);
 
 /* ---------------------------------------------------------------------------------------------
  * Timing (for bench.py / the roofline): on every `enable`-th udpdk_gpu_rx call (0 = off, 1 =

@@ -229,6 +229,54 @@ class ArpCounts(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("scanned",) + ARP_STATS[:-1] + ("announced",)]
 
 
+NEIGH_EMPTY, NEIGH_INCOMPLETE, NEIGH_REACHABLE, NEIGH_STATIC = range(4)
+NEIGH_FALLBACK = 1
+NEIGH_MAX_ENTRIES = 65536
+(NEIGH_C_SKIPPED, NEIGH_C_BCAST, NEIGH_C_MCAST, NEIGH_C_NO_ROUTE, NEIGH_C_SELF, NEIGH_C_HIT, NEIGH_C_EXPIRED,
+ NEIGH_C_INCOMPLETE, NEIGH_C_INSERTED, NEIGH_C_TABLE_FULL) = range(10)
+NEIGH_C_LOOKUP = NEIGH_C_HIT
+NEIGH_HASH_K = 0x9E3779B1
+NEIGH_LEARN_STATS = ("arp", "malformed", "bad_frame", "other_op", "sender_bad", "updated", "refreshed", "static_kept",
+                     "created", "full", "ignored")
+NEIGH_RESOLVE_STATS = ("skipped", "bcast", "mcast", "no_route", "self", "hit", "expired", "incomplete", "inserted",
+                       "table_full", "fallback", "unresolved", "requests", "no_room")
+
+
+class NeighEntry(C.Structure):
+    """udpdk_neigh_entry_t"""
+    _fields_ = [("ip", C.c_uint32), ("mac", C.c_uint8 * 6), ("state", C.c_uint8), ("pad", C.c_uint8),
+                ("stamp", C.c_uint32)]
+
+
+class NeighCfg(C.Structure):
+    """udpdk_neigh_cfg_t"""
+    _fields_ = [("src_ip", C.c_uint32), ("netmask", C.c_uint32), ("gateway", C.c_uint32), ("src_mac", C.c_uint8 * 6),
+                ("fallback_mac", C.c_uint8 * 6), ("ttl_ms", C.c_uint32), ("retrans_ms", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class NeighLearnStats(C.Structure):
+    """udpdk_neigh_learn_stats_t"""
+    _fields_ = [(k, C.c_uint32) for k in NEIGH_LEARN_STATS]
+
+
+class NeighOut(C.Structure):
+    """udpdk_neigh_out_t"""
+    _fields_ = [("dmac_dev", C.c_void_p), ("sockfd_out_dev", C.c_void_p), ("state_dev", C.c_void_p),
+                ("req_dev", C.c_void_p), ("req_origin_dev", C.c_void_p), ("req_cap", C.c_uint32)]
+
+
+class NeighResolveStats(C.Structure):
+    """udpdk_neigh_resolve_stats_t"""
+    _fields_ = [(k, C.c_uint32) for k in NEIGH_RESOLVE_STATS]
+
+
+class NeighCounts(C.Structure):
+    """udpdk_neigh_counts_t (udpdk_api.h)"""
+    _fields_ = [(k, C.c_uint64) for k in NEIGH_LEARN_STATS + NEIGH_RESOLVE_STATS[:-2] + ("no_room", "tx_unresolved",
+                                                                                        "requests")]
+
+
 class IcmpErrStats(C.Structure):
     """udpdk_icmp_err_stats_t"""
     _fields_ = [("errors", C.c_uint32), ("msg_bad", C.c_uint32), ("quote_bad", C.c_uint32), ("soft", C.c_uint32),
@@ -335,6 +383,21 @@ _PROTOS = {
     "udpdk_gpu_pipe_arp_reply": (C.c_int, [_P, C.c_int, C.POINTER(TxConfig), C.POINTER(RxBatch), _P,
                                            C.POINTER(ArpOut)]),
     "udpdk_gpu_pipe_arp_stats": (C.c_int, [_P, C.c_int, C.POINTER(ArpStats)]),
+    "udpdk_gpu_neigh_create": (C.c_int, [_P, C.c_uint32]),
+    "udpdk_gpu_neigh_set": (C.c_int, [_P, C.POINTER(NeighEntry), C.c_uint32]),
+    "udpdk_gpu_neigh_dump": (C.c_int, [_P, C.POINTER(NeighEntry), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_neigh_flush": (C.c_int, [_P, C.c_int]),
+    "udpdk_gpu_neigh_learn": (C.c_int, [_P, C.POINTER(NeighCfg), C.POINTER(RxBatch), _P, C.c_uint32]),
+    "udpdk_gpu_neigh_learn_stats": (C.c_int, [_P, C.POINTER(NeighLearnStats)]),
+    "udpdk_gpu_pipe_neigh_learn": (C.c_int, [_P, C.c_int, C.POINTER(NeighCfg), C.POINTER(RxBatch), _P, C.c_uint32]),
+    "udpdk_gpu_pipe_neigh_learn_stats": (C.c_int, [_P, C.c_int, C.POINTER(NeighLearnStats)]),
+    "udpdk_gpu_neigh_resolve": (C.c_int, [_P, C.POINTER(NeighCfg), _P, _P, C.c_uint32, C.c_uint32,
+                                          C.POINTER(NeighOut)]),
+    "udpdk_gpu_neigh_resolve_stats": (C.c_int, [_P, C.POINTER(NeighResolveStats)]),
+    "udpdk_gpu_neigh_geometry": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_neigh_class": (C.c_int, [C.POINTER(NeighCfg), C.c_uint32, C.POINTER(C.c_uint32), _P]),
+    "udpdk_gpu_tx_build_neigh": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(TxBatch), C.POINTER(TxOut), C.c_uint32,
+                                           C.c_uint32, _P]),
     "udpdk_gpu_timing_enable": (C.c_int, [_P, C.c_int]),
     "udpdk_gpu_timing_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "udpdk_gpu_rx_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
@@ -383,6 +446,10 @@ _PROTOS = {
     "udpdk_config_arp": (C.c_int, [C.c_int]),
     "udpdk_arp_announce": (C.c_int, []),
     "udpdk_arp_counts": (C.c_int, [C.POINTER(ArpCounts)]),
+    "udpdk_config_neigh": (C.c_int, [C.c_int]),
+    "udpdk_neigh_add": (C.c_int, [C.c_uint32, _P]),
+    "udpdk_neigh_flush": (C.c_int, []),
+    "udpdk_neigh_counts": (C.c_int, [C.POINTER(NeighCounts)]),
     "udpdk_sock_error_post": (C.c_int, [C.c_int, C.c_uint32, C.c_uint16, C.c_uint32]),
     "udpdk_icmp_err_counts": (C.c_int, [C.POINTER(IcmpErrCounts)]),
     "udpdk_sock_rx_inject": (C.c_int, [C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint16]),
@@ -1018,6 +1085,112 @@ def arp_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, meta, *, max_repli
             x.free()
 
 
+def neigh_cfg(src_ip: str | int, src_mac: bytes, *, netmask: str | int = 0, gateway: str | int = 0,
+              fallback_mac: bytes = bytes(6), ttl_ms: int = 30000, retrans_ms: int = 1000, flags: int = 0) -> NeighCfg:
+    """A udpdk_neigh_cfg_t; addresses as dotted strings or raw."""
+    raw = lambda a: raw_ip(a) if isinstance(a, str) else int(a)
+    return NeighCfg(raw(src_ip), raw(netmask), raw(gateway), (C.c_uint8 * 6)(*src_mac), (C.c_uint8 * 6)(*fallback_mac),
+                    ttl_ms, retrans_ms, flags)
+
+
+def neigh_geometry() -> tuple[int, int]:
+    """(frames per workgroup of the learn kernel, datagrams per workgroup of the resolve kernel)."""
+    t = C.c_uint32()
+    b = C.c_uint32()
+    _check(lib().udpdk_gpu_neigh_geometry(C.byref(t), C.byref(b)), "udpdk_gpu_neigh_geometry")
+    return t.value, b.value
+
+
+def neigh_class(cfg: NeighCfg, dst_ip: int) -> tuple[int, int, bytes]:
+    """udpdk_gpu_neigh_class: (class, next hop, MAC)."""
+    h = C.c_uint32(0xDEADBEEF)
+    mac = (C.c_uint8 * 6)(*([0xA5] * 6))
+    return lib().udpdk_gpu_neigh_class(C.byref(cfg), dst_ip, C.byref(h), mac), h.value, bytes(mac)
+
+
+def neigh_create(ctx: GpuContext, entries: int) -> int:
+    return lib().udpdk_gpu_neigh_create(ctx.handle, entries)
+
+
+def neigh_set(ctx: GpuContext, entries) -> int:
+    """entries: (raw ip, mac bytes, state, stamp) tuples."""
+    arr = (NeighEntry * max(1, len(entries)))()
+    for e, (ip, mac, state, stamp) in zip(arr, entries):
+        e.ip, e.mac, e.state, e.stamp = ip, (C.c_uint8 * 6)(*mac), state, stamp
+    return lib().udpdk_gpu_neigh_set(ctx.handle, arr, len(entries))
+
+
+def neigh_dump(ctx: GpuContext, cap: int = NEIGH_MAX_ENTRIES, as_list: bool = False):
+    """The table as a map: raw ip -> (mac, state, stamp); as_list: (ip, mac, state, stamp) in the table's order."""
+    arr = (NeighEntry * max(1, cap))()
+    n = C.c_uint32()
+    _check(lib().udpdk_gpu_neigh_dump(ctx.handle, arr, cap, C.byref(n)), "udpdk_gpu_neigh_dump")
+    if as_list:
+        return [(e.ip, bytes(e.mac), e.state, e.stamp) for e in arr[:n.value]]
+    return {e.ip: (bytes(e.mac), e.state, e.stamp) for e in arr[:n.value]}
+
+
+def neigh_flush(ctx: GpuContext, keep_static: bool = False) -> int:
+    return lib().udpdk_gpu_neigh_flush(ctx.handle, int(keep_static))
+
+
+def neigh_learn_run(ctx: GpuContext, cfg: NeighCfg, b: RxDeviceBatch, meta, now: int, *, n=None, pipe: int = 0):
+    """udpdk_gpu_neigh_learn (pipe 0) or udpdk_gpu_pipe_neigh_learn + udpdk_gpu_pipe_wait over host verdict
+    words. Returns a dict: rc of the call, rc and dict of the stats call, meta as downloaded afterwards."""
+    meta = np.ascontiguousarray(meta, np.uint32)
+    n = b.n if n is None else n
+    buf = ctx.upload(meta if meta.size else np.zeros(1, np.uint32))
+    try:
+        bt = RxBatch(b.frames.ptr, b.frames_bytes, b.offset.ptr, b.length.ptr,
+                     b.ptype.ptr if b.ptype is not None else None, n)
+        st = NeighLearnStats()
+        if pipe:
+            rc = lib().udpdk_gpu_pipe_neigh_learn(ctx.handle, pipe, C.byref(cfg), C.byref(bt), C.c_void_p(buf.ptr), now)
+            _check(lib().udpdk_gpu_pipe_wait(ctx.handle, pipe), "udpdk_gpu_pipe_wait")
+            src = lib().udpdk_gpu_pipe_neigh_learn_stats(ctx.handle, pipe, C.byref(st))
+        else:
+            rc = lib().udpdk_gpu_neigh_learn(ctx.handle, C.byref(cfg), C.byref(bt), C.c_void_p(buf.ptr), now)
+            src = lib().udpdk_gpu_neigh_learn_stats(ctx.handle, C.byref(st))
+        ctx.sync()
+        return {"rc": rc, "stats_rc": src, "stats": {k: getattr(st, k) for k in NEIGH_LEARN_STATS},
+                "meta": ctx.download(buf, np.uint32, max(1, meta.size))[:meta.size]}
+    finally:
+        buf.free()
+
+
+def neigh_resolve_run(ctx: GpuContext, cfg: NeighCfg, dst_ip, sockfd, now: int, *, req_cap=None, pad: int = 4):
+    """udpdk_gpu_neigh_resolve over host arrays. Returns a dict: rc of the call, rc and dict of the stats
+    call, dmac [n + pad, 2], sockfd_out, state, req [req_cap + pad, 64] and req_origin as downloaded, each `pad`
+    elements longer than the call may write and pre-filled with 0xA5 bytes, and dst_ip and sockfd as
+    downloaded afterwards."""
+    dst_ip = np.ascontiguousarray(dst_ip, np.uint32)
+    sockfd = np.ascontiguousarray(sockfd, np.int32)
+    n = dst_ip.size
+    req_cap = n if req_cap is None else req_cap
+    can = lambda nbytes: ctx.upload(np.full(max(nbytes, 16), 0xA5, np.uint8))
+    bufs = [ctx.upload(dst_ip if n else np.zeros(1, np.uint32)), ctx.upload(sockfd if n else np.zeros(1, np.int32)),
+            can(8 * (n + pad)), can(4 * (n + pad)), can(n + pad), can(ARP_SLOT_BYTES * (req_cap + pad)),
+            can(4 * (req_cap + pad))]
+    try:
+        o = NeighOut(bufs[2].ptr, bufs[3].ptr, bufs[4].ptr, bufs[5].ptr, bufs[6].ptr, req_cap)
+        st = NeighResolveStats()
+        rc = lib().udpdk_gpu_neigh_resolve(ctx.handle, C.byref(cfg), C.c_void_p(bufs[0].ptr), C.c_void_p(bufs[1].ptr), n,
+                                           now, C.byref(o))
+        src = lib().udpdk_gpu_neigh_resolve_stats(ctx.handle, C.byref(st))
+        ctx.sync()
+        return {"rc": rc, "stats_rc": src, "stats": {k: getattr(st, k) for k in NEIGH_RESOLVE_STATS},
+                "dmac": ctx.download(bufs[2], np.uint32, 2 * (n + pad)).reshape(-1, 2),
+                "sockfd_out": ctx.download(bufs[3], np.int32, n + pad),
+                "state": ctx.download(bufs[4], np.uint8, n + pad),
+                "req": ctx.download(bufs[5], np.uint8, ARP_SLOT_BYTES * (req_cap + pad)).reshape(-1, ARP_SLOT_BYTES),
+                "req_origin": ctx.download(bufs[6], np.uint32, req_cap + pad),
+                "dst_ip": ctx.download(bufs[0], np.uint32, max(1, n))[:n],
+                "sockfd": ctx.download(bufs[1], np.int32, max(1, n))[:n]}
+    finally:
+        for x in bufs:
+            x.free()
+
+
 def icmp_errno(code: int) -> tuple[int, int]:
     """udpdk_gpu_icmp_errno: (errno, hard) of a destination-unreachable code."""
     h = C.c_int(-1)
@@ -1323,6 +1496,22 @@ class HostApi:
         c = ArpCounts()
         _check(self.L.udpdk_arp_counts(C.byref(c)), "udpdk_arp_counts")
         return c
+
+    def config_neigh(self, mode: int) -> int:
+        """The neighbour cache (udpdk_config_neigh: 0 off, 1 strict, 2 fallback): returns the previous mode; a
+        negative argument only reads it."""
+        return self.L.udpdk_config_neigh(int(mode))
+
+    def neigh_add(self, ip: str | int, mac: bytes) -> int:
+        return self.L.udpdk_neigh_add(raw_ip(ip) if isinstance(ip, str) else ip, (C.c_uint8 * 6)(*mac))
+
+    def neigh_flush(self) -> int:
+        return self.L.udpdk_neigh_flush()
+
+    def neigh_counts(self) -> dict[str, int]:
+        c = NeighCounts()
+        _check(self.L.udpdk_neigh_counts(C.byref(c)), "udpdk_neigh_counts")
+        return {k: int(getattr(c, k)) for k, _ in NeighCounts._fields_}
 
     def tx_pending(self) -> int:
         return int(self.L.udpdk_tx_pending())

@@ -265,6 +265,17 @@ struct h_state {
     udpdk_arp_counts_t arp_counts;
     void     *ar_out_d, *ar_h;
     uint64_t  ar_out_d_cap, ar_h_cap;
+    /* Neighbours (neigh.c): [gpu] neigh / udpdk_config_neigh (UDPDK_NEIGH_MODE_*; off: a poll and a drain
+     * enqueue what they always did), the table's size and timers, [port0] netmask / gateway (raw; 0: all
+     * on-link / none), whether the main context has its table yet, the session's counts (under tx_lock);
+     * udpdk_tx_drain's work buffers, grow-only: the device MACs + sockets + states + requests + origins
+     * and the pinned readback */
+    uint32_t  neigh_mode, neigh_entries, neigh_ttl_ms, neigh_retrans_ms;
+    uint32_t  netmask, gateway;
+    int       neigh_ready;
+    udpdk_neigh_counts_t neigh_counts;
+    void     *ng_d, *ng_h;
+    uint64_t  ng_d_cap, ng_h_cap;
     /* ICMP errors received (rx_icmp_err.c): [gpu] icmp_errors / udpdk_config_icmp_errors (0: a poll
      * enqueues what it always did), the session's counts (under lock) and the peer records the
      * contexts hold (h_peer_apply: what an error is posted against); work buffers, grow-only, one
@@ -348,6 +359,20 @@ int  h_icmp_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const u
 void h_arp_reset(void);                   /* under tx_lock */
 void h_arp_buffers_free(void);
 int  h_arp_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const uint32_t *meta_dev, uint64_t not_ipv4);
+
+/* neigh.c */
+#define H_NEIGH_ENTRIES_DEFAULT 1024u
+#define H_NEIGH_TTL_MS_DEFAULT 30000u
+#define H_NEIGH_RETRANS_MS_DEFAULT 1000u
+#define H_NEIGH_REQ_CAP 256u              /* who-has frames one drain can queue (the rest: no_room) */
+#define H_NEIGH_REQ_FIRST 32u             /* ... copied back behind the stage, before the counts are known */
+void h_neigh_reset(void);                 /* under tx_lock */
+void h_neigh_buffers_free(void);
+uint32_t h_neigh_now(void);
+void h_neigh_cfg(udpdk_neigh_cfg_t *cfg);
+int  h_neigh_table(void);
+int  h_neigh_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const uint32_t *meta_dev, uint64_t not_ipv4);
+void h_neigh_count_resolve(const udpdk_neigh_resolve_stats_t *st);   /* under tx_lock */
 
 /* rx_icmp_err.c */
 void h_icmp_err_reset(void);              /* under g_udpdk.lock */

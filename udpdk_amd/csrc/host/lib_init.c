@@ -47,6 +47,11 @@ static void h_config_defaults(void)
     g_udpdk.icmp_errors = 0;           /* received ICMP errors are forgotten, as in the reference */
     g_udpdk.arp_on = 0;                /* ARP requests are not answered, as in the reference */
     g_udpdk.arp_announce = 0;
+    g_udpdk.neigh_mode = UDPDK_NEIGH_MODE_OFF;   /* every frame to the [port0_dst] MAC, as in the reference */
+    g_udpdk.neigh_entries = H_NEIGH_ENTRIES_DEFAULT;
+    g_udpdk.neigh_ttl_ms = H_NEIGH_TTL_MS_DEFAULT;
+    g_udpdk.neigh_retrans_ms = H_NEIGH_RETRANS_MS_DEFAULT;
+    g_udpdk.netmask = g_udpdk.gateway = 0;
     g_udpdk.arena_bytes_max = 4ull << 30;
     g_udpdk.arena_count_max = 1024;
     g_udpdk.port_spec[0] = g_udpdk.port_peer[0] = 0;
@@ -77,6 +82,7 @@ void udpdk_host_reset(void)
     h_icmp_reset();
     h_icmp_err_reset();
     h_arp_reset();
+    h_neigh_reset();
     pthread_mutex_unlock(&g_udpdk.tx_lock);
     atomic_store(&g_udpdk.interrupted, 0);
     g_udpdk.snap_version = UINT64_MAX;
@@ -88,6 +94,7 @@ void udpdk_host_reset(void)
     g_udpdk.icmp_burst = H_ICMP_BURST_DEFAULT;
     g_udpdk.icmp_errors = 0;
     g_udpdk.arp_on = 0;
+    g_udpdk.neigh_mode = UDPDK_NEIGH_MODE_OFF;
     pthread_mutex_unlock(&g_udpdk.lock);
 }
 
@@ -266,6 +273,12 @@ static int h_load_ini(const char *path)
             g_udpdk.src_ip = inet_addr(v);
         } else if (!strcmp(section, "port0_dst") && !strcmp(k, "mac_addr")) {
             if (h_parse_mac(v, g_udpdk.dst_mac)) { rc = -1; break; }
+        } else if (!strcmp(section, "port0") && (!strcmp(k, "netmask") || !strcmp(k, "gateway"))) {
+            /* what udpdk_tx_drain's neighbour resolution takes for on-link ([gpu] neigh); 0.0.0.0
+             * (default): everything is on-link / no gateway */
+            struct in_addr a;
+            if (!inet_aton(v, &a)) { rc = -1; break; }
+            *(k[0] == 'n' ? &g_udpdk.netmask : &g_udpdk.gateway) = a.s_addr;
         } else if (!strcmp(section, "port0") && !strcmp(k, "mtu")) {
             if (udpdk_config_mtu((uint32_t)strtoul(v, NULL, 0))) { rc = -1; break; }
         } else if (!strcmp(section, "gpu") && !strcmp(k, "device")) {
@@ -345,6 +358,24 @@ static int h_load_ini(const char *path)
             /* 1: udpdk_init queues one RFC 5227 announcement of our address (udpdk_arp_announce) */
             if (!strcmp(v, "0") || !strcmp(v, "1")) g_udpdk.arp_announce = (uint32_t)(v[0] - '0');
             else { rc = -1; break; }
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "neigh")) {
+            /* 1: a poll learns neighbours from ARP and a drain resolves every datagram's MAC, dropping
+             * what it cannot resolve; fallback: those go to the [port0_dst] MAC; 0 (default); checked
+             * against [gpu] devices once the file is read */
+            if (!strcmp(v, "0")) g_udpdk.neigh_mode = UDPDK_NEIGH_MODE_OFF;
+            else if (!strcmp(v, "1")) g_udpdk.neigh_mode = UDPDK_NEIGH_MODE_STRICT;
+            else if (!strcmp(v, "fallback")) g_udpdk.neigh_mode = UDPDK_NEIGH_MODE_FALLBACK;
+            else { rc = -1; break; }
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "neigh_entries")) {
+            char *e;
+            const unsigned long x = strtoul(v, &e, 0);
+            if (e == v || *e || x < 8u || x > UDPDK_NEIGH_MAX_ENTRIES || (x & (x - 1u))) { rc = -1; break; }
+            g_udpdk.neigh_entries = (uint32_t)x;
+        } else if (!strcmp(section, "gpu") && (!strcmp(k, "neigh_ttl_ms") || !strcmp(k, "neigh_retrans_ms"))) {
+            char *e;
+            const unsigned long x = strtoul(v, &e, 0);
+            if (e == v || *e || x > 0xFFFFFFFFul) { rc = -1; break; }
+            *(k[6] == 't' ? &g_udpdk.neigh_ttl_ms : &g_udpdk.neigh_retrans_ms) = (uint32_t)x;
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port")) {
             snprintf(g_udpdk.port_spec, sizeof(g_udpdk.port_spec), "%s", v);
         } else if (!strcmp(section, "gpu") && !strcmp(k, "port_peer")) {
@@ -363,6 +394,8 @@ static int h_load_ini(const char *path)
     if (!rc && g_udpdk.icmp_errors && g_udpdk.n_shards > 1) rc = -2;
     /* ... and do not answer ARP (udpdk_config_arp: ENOTSUP; here EINVAL, as for [gpu] icmp) */
     if (!rc && g_udpdk.arp_on && g_udpdk.n_shards > 1) rc = -1;
+    /* ... and learn no neighbours (udpdk_config_neigh: ENOTSUP; here EINVAL, as for [gpu] arp) */
+    if (!rc && g_udpdk.neigh_mode && g_udpdk.n_shards > 1) rc = -1;
     return rc;
 }
 
@@ -385,6 +418,7 @@ int udpdk_init(int argc, char *argv[])
     g_udpdk.rx_drop_applied = 0;       /* new contexts drop nothing until a poll sets them */
     g_udpdk.reuseport_applied = UDPDK_REUSEPORT_FANOUT;   /* ... and balance nothing */
     g_udpdk.peer_applied = 0;          /* ... and hold no peer table */
+    g_udpdk.neigh_ready = 0;           /* ... and no neighbour table */
     /* [gpu] devices with two or more entries: one RX shard context per entry (SURVEY.md §7 step
      * 8); a poll splits its batch into that many contiguous shards */
     if (g_udpdk.n_shards > 1) {
@@ -478,6 +512,7 @@ void udpdk_cleanup(void)
     h_icmp_buffers_free();
     h_icmp_err_buffers_free();
     h_arp_buffers_free();
+    h_neigh_buffers_free();
     h_arenas_free_all();
     g_udpdk.frag_ready = 0;
     h_shards_destroy();

@@ -1239,6 +1239,11 @@ static int h_poll_chunked(const uint8_t *frames, uint64_t frames_bytes, const ui
             err = errno;
             break;
         }
+        /* [gpu] neigh: what the chunk's ARP teaches, behind its replies on the same pipe */
+        if (h_neigh_stage(g, h_pipe_of(k), &staged, meta_dev, C->st.counters[UDPDK_C_VERDICT0 + UDPDK_V_NOT_IPV4])) {
+            err = errno;
+            break;
+        }
         /* [gpu] icmp: the chunk's answers, on its pipe, before reassembly touches the frames */
         if (h_icmp_stage(g, h_pipe_of(k), &staged, meta_dev, &icmp_budget)) { err = errno; break; }
         /* [gpu] icmp_errors: the chunk's ICMP errors for connected sockets, on its pipe */
@@ -1381,6 +1386,8 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
         /* [gpu] arp: replies to the staged batch's requests for our address, queued ahead of its ICMP
          * answers (nothing is enqueued with the switch off or for a batch of pure IPv4) */
         if (h_arp_stage(g, 0, &staged, meta_dev, st.counters[UDPDK_C_VERDICT0 + UDPDK_V_NOT_IPV4])) goto out;
+        /* [gpu] neigh: what the batch's ARP teaches the neighbour table, under the same gate */
+        if (h_neigh_stage(g, 0, &staged, meta_dev, st.counters[UDPDK_C_VERDICT0 + UDPDK_V_NOT_IPV4])) goto out;
         /* [gpu] icmp: echo replies and port-unreachable errors for the staged batch, queued for
          * udpdk_tx_drain, before reassembly touches the frames (nothing is enqueued with flags 0) */
         uint32_t icmp_budget = h_icmp_budget();

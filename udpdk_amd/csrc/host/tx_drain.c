@@ -13,6 +13,14 @@
  * ARP and ICMP frames a poll built (rx_arp.c, rx_icmp.c) and the ARP announcement leave first, oldest
  * first, copied from their host queue; the socket datagrams follow in what room is left. A queued frame that does not fit the caller's
  * limits stays queued, and the datagrams wait behind it for the next drain.
+ *
+ * With [gpu] neigh on, the build is preceded by udpdk_gpu_neigh_resolve on the same stream and done by
+ * udpdk_gpu_tx_build_neigh: every datagram's frames carry its next hop's MAC. The resolved sockets and
+ * the first who-has requests come back behind the frames and the counts in the same wait. A datagram
+ * that came out without a socket (no MAC in strict mode, no route) is left out of the frame table,
+ * dequeued and counted like the others the drain cannot send; its span in the output is a gap. The
+ * requests go onto the host queue and leave first in the next drain. Off, the drain calls what it
+ * always called.
  */
 #include <errno.h>
 #include <stdlib.h>
@@ -56,6 +64,7 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
     udpdk_gpu_ctx *g = g_udpdk.gpu;
     const uint32_t mtu = g_udpdk.mtu;
     const uint32_t txf = g_udpdk.tx_udp_cksum ? UDPDK_TX_UDP_CKSUM : 0u;
+    const int neigh = g_udpdk.neigh_mode != UDPDK_NEIGH_MODE_OFF;
     /* the slot table the TX kernel reads (source port and address per socket). tx_lock is taken
      * before the table lock is dropped (the order udpdk_close uses): a sendto that auto-binds, or
      * a close + socket + bind, either lands before the refresh (and is in the uploaded table) or
@@ -171,7 +180,50 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
                           (const int32_t *)(d + o_sock), (const uint32_t *)(d + o_ip),
                           (const uint16_t *)(d + o_port), nsel};
     udpdk_tx_out_t o = {g_udpdk.tx_fr_d, bytes + 64, (const uint32_t *)(d + o_foff)};
-    if ((rc = udpdk_gpu_h2d(g, d, h, tot)) || (rc = udpdk_gpu_tx_build_flags(g, &cfg, &b, &o, mtu, txf)) ||
+    const int32_t *sock_out = NULL;
+    if (neigh) {
+        /* device: MACs, resolved sockets, states, request slots, origins; pinned: sockets, slots */
+        const uint64_t n_mac = 0, n_sock = a16(8ull * nsel), n_state = n_sock + a16(4ull * nsel),
+                       n_req = n_state + a16(nsel), n_org = n_req + (uint64_t)H_NEIGH_REQ_CAP * UDPDK_ARP_SLOT_BYTES,
+                       n_tot = n_org + 4ull * H_NEIGH_REQ_CAP;
+        const uint64_t hq = a16(4ull * nsel), first = (uint64_t)H_NEIGH_REQ_FIRST * UDPDK_ARP_SLOT_BYTES;
+        if (h_neigh_table() || h_grow_dev(&g_udpdk.ng_d, &g_udpdk.ng_d_cap, n_tot) ||
+            h_grow_pinned(&g_udpdk.ng_h, &g_udpdk.ng_h_cap, hq + (uint64_t)H_NEIGH_REQ_CAP * UDPDK_ARP_SLOT_BYTES))
+            goto out;
+        uint8_t *nd = g_udpdk.ng_d, *nh = g_udpdk.ng_h;
+        udpdk_neigh_cfg_t ncfg;
+        h_neigh_cfg(&ncfg);
+        const udpdk_neigh_out_t no = {(uint32_t *)(nd + n_mac), (int32_t *)(nd + n_sock), nd + n_state, nd + n_req,
+                                      (uint32_t *)(nd + n_org), H_NEIGH_REQ_CAP};
+        udpdk_neigh_resolve_stats_t nst;
+        b.sockfd_dev = no.sockfd_out_dev;
+        if ((rc = udpdk_gpu_h2d(g, d, h, tot)) ||
+            (rc = udpdk_gpu_neigh_resolve(g, &ncfg, (const uint32_t *)(d + o_ip), (const int32_t *)(d + o_sock), nsel,
+                                          h_neigh_now(), &no)) ||
+            (rc = udpdk_gpu_tx_build_neigh(g, &cfg, &b, &o, mtu, txf, no.dmac_dev)) ||
+            (rc = udpdk_gpu_d2h(g, out + b0, g_udpdk.tx_fr_d, bytes)) ||
+            (rc = udpdk_gpu_d2h(g, nh, no.sockfd_out_dev, 4ull * nsel)) ||
+            (rc = udpdk_gpu_d2h(g, nh + hq, no.req_dev, first))) {
+            errno = -rc;
+            goto out;
+        }
+        rc = udpdk_gpu_neigh_resolve_stats(g, &nst);               /* (waits for all of the above) */
+        if (rc && rc != -ENOSPC) { errno = -rc; goto out; }       /* (-ENOSPC: the excess is no_room) */
+        if (nst.requests > H_NEIGH_REQ_CAP) { errno = EIO; goto out; }
+        if (nst.requests > H_NEIGH_REQ_FIRST &&
+            ((rc = udpdk_gpu_d2h(g, nh + hq + first, no.req_dev + first,
+                                 (uint64_t)(nst.requests - H_NEIGH_REQ_FIRST) * UDPDK_ARP_SLOT_BYTES)) ||
+             (rc = udpdk_gpu_sync(g)))) {
+            errno = -rc;
+            goto out;
+        }
+        if (nst.requests && !g_udpdk.icmpq.buf && h_icmpq_init(&g_udpdk.icmpq, H_ICMPQ_BYTES)) { errno = ENOMEM; goto out; }
+        for (uint32_t r = 0; r < nst.requests; r++)
+            if (!h_icmpq_push(&g_udpdk.icmpq, nh + hq + (uint64_t)r * UDPDK_ARP_SLOT_BYTES, UDPDK_ARP_FRAME_BYTES))
+                g_udpdk.neigh_counts.requests++;
+        h_neigh_count_resolve(&nst);
+        sock_out = (const int32_t *)nh;
+    } else if ((rc = udpdk_gpu_h2d(g, d, h, tot)) || (rc = udpdk_gpu_tx_build_flags(g, &cfg, &b, &o, mtu, txf)) ||
         (rc = udpdk_gpu_d2h(g, out + b0, g_udpdk.tx_fr_d, bytes)) || (rc = udpdk_gpu_sync(g))) {
         errno = -rc;
         goto out;
@@ -181,6 +233,10 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
     for (uint32_t i = 0; i < nsel; i++) {
         const uint32_t nf = g_udpdk.tx_sel[i].nf;
         const uint64_t span = udpdk_gpu_tx_span(len[i], mtu, NULL);
+        if (sock_out && sock_out[i] < 0) {                  /* unresolved: nothing was built for it */
+            g_udpdk.neigh_counts.tx_unresolved++;
+            continue;
+        }
         for (uint32_t f = 0; f < nf; f++) {
             out_off[k] = (uint32_t)b0 + foff[i] + f * (mtu + 14u);
             out_len[k] = (uint16_t)(f + 1 < nf ? mtu + 14u : span - (uint64_t)(nf - 1) * (mtu + 14u));

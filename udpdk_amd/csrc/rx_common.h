@@ -321,6 +321,14 @@ struct TxArgs {
     uint32_t parts;            // waves sharing one group of 64 datagrams' chunk sweep (>= 1)
 };
 
+// udpdk_gpu_tx_build_neigh: TxArgs and the datagrams' own destination MACs
+struct TxNeighArgs : TxArgs {
+    const uint32_t *dmac;      // [2 n] MAC bytes 0-3, then 4-5 in the low half (8-byte aligned)
+};
+template <bool DM> struct TxArgsSel { using type = TxArgs; };
+template <> struct TxArgsSel<true> { using type = TxNeighArgs; };
+template <bool DM> using TxArgsFor = typename TxArgsSel<DM>::type;
+
 // Payload delivery (rx_gather): lane entries [first, first + count) -> payload slots + source
 // addresses (the batch form of udpdk_recvfrom, udpdk_syscall.c:401-488).
 constexpr int GATHER_BLOCK = 256;
@@ -428,7 +436,8 @@ int  reasm_run(Reasm *r, hipStream_t st, const udpdk_rx_batch_t *bt, const uint3
                 uint64_t tms, udpdk_reasm_out_t *o, int *hip_err, bool inplace);
 
 // CK: with the UDP checksum (UDPDK_TX_UDP_CKSUM; one wave per group, TxArgs::parts unused)
-template <bool CK> __global__ void tx_build(TxArgs a);
+// DM: with per-datagram destination MACs (TxNeighArgs)
+template <bool CK, bool DM> __global__ void tx_build(TxArgsFor<DM> a);
 
 // Reply plan (tx_reply.hip): lane entries [first, first + count) -> the descriptor arrays of a
 // udpdk_tx_batch_t whose payloads are the received frames' own bytes.

@@ -89,9 +89,10 @@ constexpr uint32_t TX_SMALL_LOADS = (TX_SMALL_SPAN - 42u + 15u) / 16u;
 // the slot lookup (byte-aligned 16-byte buffer loads; pieces past the payload are addressed out
 // of range, so they cost no memory access and read as 0), so a wave's frames take one round
 // trip after the descriptors instead of one per 64-chunk sweep step.
-template <bool CK>
+// DM: bytes 0-5 are the datagram's own (dm_lo, dm_hi: TxNeighArgs::dmac) instead of the config's.
+template <bool CK, bool DM>
 __device__ __forceinline__ void tx_small(const TxArgs &a, uint32_t i, uint32_t fo, uint32_t L,
-                                         uint32_t po, int32_t sock)
+                                         uint32_t po, int32_t sock, uint32_t dm_lo, uint32_t dm_hi)
 {
     const __amdgpu_buffer_rsrc_t pr = make_rsrc(a.payload, a.payload_rsrc);
     const __amdgpu_buffer_rsrc_t fw = make_rsrc(a.frames, a.frames_bytes);
@@ -118,6 +119,10 @@ __device__ __forceinline__ void tx_small(const TxArgs &a, uint32_t i, uint32_t f
     const uint32_t tl = L + 28u, ul = L + 8u;                                      // :336, :344
     uint32_t H[10];
     H[0] = a.mac_lo[0]; H[1] = a.mac_lo[1]; H[2] = a.mac_lo[2];                    // :315-317
+    if constexpr (DM) {
+        H[0] = dm_lo;
+        H[1] = (dm_hi & 0xFFFFu) | (a.mac_lo[1] & 0xFFFF0000u);
+    }
     H[3] = 0x00450008u;
     H[4] = bswap16(tl);
     H[5] = 0x11400000u;
@@ -178,9 +183,13 @@ __device__ __forceinline__ void tx_small(const TxArgs &a, uint32_t i, uint32_t f
 // byte t of a datagram sits in an odd byte of its chunk's 16-bit words exactly when frame_off[i]
 // is odd, in every frame of the datagram: the chunk's folded sum is byte-swapped then (RFC 1071
 // §2(B)). One wave per group (parts is 1): the patch must follow the sweep's own zeros.
-template <bool CK>
+//
+// DM: the destination MAC of every frame of datagram i is a.dmac[2 i], a.dmac[2 i + 1]
+// (udpdk_gpu_tx_build_neigh) instead of the config's; the argument block is TxNeighArgs then, and
+// the forms without it take TxArgs and compile to what they were.
+template <bool CK, bool DM>
 __global__ void __launch_bounds__(TX_BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8)))
-tx_build(TxArgs a)
+tx_build(TxArgsFor<DM> a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t win[TXW][64][TX_WIN / 4];
     // per output frame of the current round
@@ -203,15 +212,21 @@ tx_build(TxArgs a)
         const uint32_t i = g * 64 + lane;
         uint32_t nf = 0, fo = 0, L = 0, po = 0, src = 0, dst = 0, pt = 0;
         int32_t sock = -1;
+        uint32_t dm_lo = 0, dm_hi = 0;
         if (i < a.n) {
             fo = a.frame_off[i];
             L = a.payload_len[i];
             po = a.payload_off[i];
             sock = a.sockfd[i];
+            if constexpr (DM) {
+                const uint2 dm = *reinterpret_cast<const uint2 *>(a.dmac + 2ull * i);
+                dm_lo = dm.x;
+                dm_hi = dm.y;
+            }
         }
         // a wave of small unfragmented frames: one lane builds and stores its own frame
         if (!__ballot(i < a.n && (L + 42u > TX_SMALL_SPAN || (a.mtu && L + 42u > a.mtu)))) {
-            if (part == 0u) tx_small<CK>(a, i, fo, L, po, sock);
+            if (part == 0u) tx_small<CK, DM>(a, i, fo, L, po, sock, dm_lo, dm_hi);
             continue;
         }
         // this group's accumulators; the first round's wave_sync_tx orders them before any add
@@ -244,6 +259,7 @@ tx_build(TxArgs a)
             const uint32_t f = r0 + lane;
             uint32_t nch = 0, ffo = 0, plen = 0, ppo = 0, hl = 0;
             uint32_t k = 0, lnq = ln, sq = src, dq = dst, ptq = pt, foq = fo, poq = po;
+            uint32_t mlq = dm_lo, mhq = dm_hi;
             bool act = nf != 0;
             uint32_t dl = lane;                   // the frame's datagram lane (CK)
             if (!direct) {
@@ -263,6 +279,10 @@ tx_build(TxArgs a)
                 ptq = __shfl(pt, (int)q, 64);
                 foq = __shfl(fo, (int)q, 64);
                 poq = __shfl(po, (int)q, 64);
+                if constexpr (DM) {
+                    mlq = __shfl(dm_lo, (int)q, 64);
+                    mhq = __shfl(dm_hi, (int)q, 64);
+                }
                 act = f < n_frames;
                 dl = q;
             }
@@ -292,6 +312,10 @@ tx_build(TxArgs a)
                 const uint32_t ul = Lq + 8u;                                     // :344
                 uint32_t h[12];
                 h[0] = a.mac_lo[0]; h[1] = a.mac_lo[1]; h[2] = a.mac_lo[2];      // :315-317
+                if constexpr (DM) {
+                    h[0] = mlq;
+                    h[1] = (mhq & 0xFFFFu) | (a.mac_lo[1] & 0xFFFF0000u);
+                }
                 h[3] = 0x00450008u;                                 // type 0x0800, 0x45, tos 0
                 h[4] = bswap16(tl);                                 // total length, id 0
                 h[5] = bswap16(ff) | 0x11400000u;                   // fragment field, ttl 64, 17
@@ -411,7 +435,9 @@ tx_build(TxArgs a)
     }
 }
 
-template __global__ void tx_build<false>(TxArgs a);
-template __global__ void tx_build<true>(TxArgs a);
+template __global__ void tx_build<false, false>(TxArgs a);
+template __global__ void tx_build<true, false>(TxArgs a);
+template __global__ void tx_build<false, true>(TxNeighArgs a);
+template __global__ void tx_build<true, true>(TxNeighArgs a);
 
 } // namespace udpdk

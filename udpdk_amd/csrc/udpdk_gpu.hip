@@ -25,6 +25,7 @@
 #include "icmp_reply.h"
 #include "icmp_error.h"
 #include "arp_reply.h"
+#include "neigh.h"
 #include "rss_host.h"
 
 using namespace udpdk;
@@ -180,6 +181,20 @@ struct ArpWs {
     void release() { release_all(cand, row, fuse, res); }
 };
 
+// Workspaces of the neighbour stages (neigh.hip), lazily sized: the learn stage has one for the
+// context stream (udpdk_gpu_neigh_learn) and one per pipe (udpdk_gpu_pipe_neigh_learn), the resolve
+// stage one (the context stream).
+template <typename E, typename R>
+struct NeighWs {
+    DevBuf<E> cand;
+    DevBuf<uint32_t> row;                      // the rows, then rbase
+    DevBuf<unsigned long long> fuse;           // fan-in words, zeroed once: every launch leaves zeros
+    ResultSlot<R> res;
+    void release() { release_all(cand, row, fuse, res); }
+};
+using NeighLearnWs = NeighWs<uint4, NeighLearnResult>;
+using NeighResolveWs = NeighWs<uint2, NeighResolveResult>;
+
 // The sticky lane-removal stages, in the order rx_on_pipe applies them.
 enum { ST_DROP, ST_BALANCE, ST_PEER, N_STICKY };
 
@@ -221,10 +236,11 @@ struct Pipe {
     IcmpWs icmp;                              // udpdk_gpu_pipe_icmp_reply on this pipe's stream
     IcmpErrWs icmp_err;                       // udpdk_gpu_pipe_icmp_errors on this pipe's stream
     ArpWs arp;                                // udpdk_gpu_pipe_arp_reply on this pipe's stream
+    NeighLearnWs nlearn;                      // udpdk_gpu_pipe_neigh_learn on this pipe's stream
     void release()
     {
         release_all(hist, partial, base, agg, ticket, fuse, tile_cnt, res, flt, bal, peer, st_frames_d,
-                    st_desc_d, st_out_d, st_frames_h, st_desc_h, icmp, icmp_err, arp);
+                    st_desc_d, st_out_d, st_frames_h, st_desc_h, icmp, icmp_err, arp, nlearn);
     }
 };
 constexpr int MAX_PIPES = 4;
@@ -288,6 +304,10 @@ struct udpdk_gpu_ctx {
     IcmpWs icmp;                              // udpdk_gpu_icmp_reply (the context stream)
     IcmpErrWs icmp_err;                       // udpdk_gpu_icmp_errors (the context stream)
     ArpWs arp;                                // udpdk_gpu_arp_reply (the context stream)
+    DevBuf<uint32_t> neigh_tab;               // udpdk_gpu_neigh_create: four dwords per entry
+    uint32_t neigh_entries = 0;               // 0: no table
+    NeighLearnWs nlearn;                      // udpdk_gpu_neigh_learn (the context stream)
+    NeighResolveWs nresolve;                  // udpdk_gpu_neigh_resolve
 
     unsigned long long *dbg = nullptr;        // diagnostic stamp buffer (UDPDK_STAMPS builds)
     Reasm *reasm = nullptr;                   // udpdk_gpu_frag_table_create
@@ -315,7 +335,7 @@ struct udpdk_gpu_ctx {
     {
         for (Pipe &P : pipes) P.release();
         release_all(port_tab, binds, slots, hint, xflt, bal_rp, bal_ktab, xbal, peer_tab, xpeer, rpl, icmp,
-                    icmp_err, arp, rss_reta, rss_ktab, rss_qid, rss_hist, rss_partial, rss_total, rss_fuse);
+                    icmp_err, arp, neigh_tab, nlearn, nresolve, rss_reta, rss_ktab, rss_qid, rss_hist, rss_partial, rss_total, rss_fuse);
     }
 };
 
@@ -1880,7 +1900,15 @@ int udpdk_gpu_tx_build_flags(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
                              const udpdk_tx_batch_t *bt, const udpdk_tx_out_t *o, uint32_t mtu,
                              uint32_t flags)
 {
+    return udpdk_gpu_tx_build_neigh(c, cfg, bt, o, mtu, flags, nullptr);
+}
+
+int udpdk_gpu_tx_build_neigh(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
+                             const udpdk_tx_batch_t *bt, const udpdk_tx_out_t *o, uint32_t mtu,
+                             uint32_t flags, const uint32_t *dmac_dev)
+{
     if (!c || !cfg || !bt || !o) return -EINVAL;
+    if ((uintptr_t)dmac_dev & 7u) return -EINVAL;
     if (flags & ~UDPDK_TX_UDP_CKSUM) return -EINVAL;
     if (mtu && (mtu < 68u || mtu > 65535u || (mtu - 20u) % 8u)) return -EINVAL;
     if (!bt->n) return 0;
@@ -1890,7 +1918,8 @@ int udpdk_gpu_tx_build_flags(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
     if (bt->payload_bytes >= (1ull << 32) || o->frames_bytes >= (1ull << 32)) return -EINVAL;
     if (((uintptr_t)o->frames_dev & 15u) || ((uintptr_t)bt->payload_dev & 15u)) return -EINVAL;
     { int r = on_ctx_stream(c); if (r) return r; }
-    TxArgs ta;
+    TxNeighArgs ta;
+    ta.dmac = dmac_dev;
     ta.payload = bt->payload_dev;
     ta.payload_off = bt->payload_off_dev;
     ta.payload_len = bt->payload_len_dev;
@@ -1923,9 +1952,16 @@ int udpdk_gpu_tx_build_flags(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg,
     // it and patched in behind that wave's own stores); UDPDK_TX_PARTS does not apply
     if (flags & UDPDK_TX_UDP_CKSUM) ta.parts = 1u;
     const uint32_t grid = std::min<uint32_t>(ceil_div(groups * ta.parts, TX_BLOCK / 64), c->knobs.tx_grid);
+    // (without MACs of their own the datagrams take the forms, and the argument block, they always took)
+    if (dmac_dev) {
+        if (flags & UDPDK_TX_UDP_CKSUM)
+            return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<true, true>, dim3(grid), dim3(TX_BLOCK), ta);
+        return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<false, true>, dim3(grid), dim3(TX_BLOCK), ta);
+    }
+    const TxArgs &tb = ta;
     if (flags & UDPDK_TX_UDP_CKSUM)
-        return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<true>, dim3(grid), dim3(TX_BLOCK), ta);
-    return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<false>, dim3(grid), dim3(TX_BLOCK), ta);
+        return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<true, false>, dim3(grid), dim3(TX_BLOCK), tb);
+    return launch_timed(c, c->stream, UDPDK_K_TX_BUILD, tx_build<false, false>, dim3(grid), dim3(TX_BLOCK), tb);
 }
 
 namespace {
@@ -2432,6 +2468,328 @@ int udpdk_gpu_pipe_arp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_arp_stats_t *st)
     if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
     const ResultSlot<ArpResult> &R = c->pipes[pipe].arp.res;
     return R.ran ? arp_stats_out(R.host, st) : -ENOENT;
+}
+
+namespace {
+
+uint32_t neigh_shift(uint32_t entries) { return 32u - (uint32_t)__builtin_ctz(entries); }
+
+void mac_words(const uint8_t *mac, uint32_t *lo, uint32_t *hi)
+{
+    *lo = *hi = 0u;
+    memcpy(lo, mac, 4);
+    memcpy(hi, mac + 4, 2);
+}
+
+// The table on the host (set, dump, flush): a copy, waited for. All streams are drained first, so
+// no kernel is the table's writer meanwhile.
+int neigh_fetch(udpdk_gpu_ctx *c, std::vector<udpdk_neigh_entry_t> &t)
+{
+    if (!c || !c->neigh_entries) return -EINVAL;
+    HIPC(c, hipSetDevice(c->device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    t.resize(c->neigh_entries);
+    HIPC(c, hipMemcpy(t.data(), c->neigh_tab, t.size() * sizeof(t[0]), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int neigh_store(udpdk_gpu_ctx *c, const std::vector<udpdk_neigh_entry_t> &t)
+{
+    HIPC(c, hipMemcpy(c->neigh_tab, t.data(), t.size() * sizeof(t[0]), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// The kernels' probe sequence on the host copy: the slot of e.ip, or the first empty one.
+int neigh_put(std::vector<udpdk_neigh_entry_t> &t, const udpdk_neigh_entry_t &e)
+{
+    const uint32_t mask = (uint32_t)t.size() - 1u;
+    uint32_t s = neigh_home(e.ip, neigh_shift((uint32_t)t.size()));
+    for (uint32_t k = 0; k <= mask; ++k, s = (s + 1u) & mask) {
+        if (t[s].ip != e.ip && t[s].ip != 0u) continue;
+        t[s] = e;
+        t[s].pad = 0;
+        return 0;
+    }
+    return -ENOSPC;
+}
+
+int neigh_cfg_check(const udpdk_gpu_ctx *c, const udpdk_neigh_cfg_t *cfg)
+{
+    if (!c || !cfg || !c->neigh_entries) return -EINVAL;
+    if (cfg->src_ip == 0u || (cfg->flags & ~UDPDK_NEIGH_FALLBACK)) return -EINVAL;
+    return 0;
+}
+
+int neigh_learn_check(const udpdk_gpu_ctx *c, const udpdk_neigh_cfg_t *cfg, const udpdk_rx_batch_t *bt,
+                      const uint32_t *meta_dev)
+{
+    const int rc = neigh_cfg_check(c, cfg);
+    if (rc) return rc;
+    if (!bt || !meta_dev || bt->frames_bytes >= (1ull << 32)) return -EINVAL;
+    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
+    return 0;
+}
+
+// A neighbour workspace for nb workgroups of `tile` units, at least what max_frames needs
+extern "C++" template <typename W>
+int neigh_ws(udpdk_gpu_ctx *c, W &ws, hipStream_t st, uint32_t n, uint32_t tile, uint32_t row_fields)
+{
+    const size_t rows = std::max<size_t>(ceil_div(std::max(n, c->max_frames), tile), 1);
+    int rc;
+    if ((rc = ws.cand.ensure(c, rows * tile)) || (rc = ws.row.ensure(c, rows * (row_fields + 1))) ||
+        (rc = ws.res.ensure(c)))
+        return rc;
+    if (!ws.fuse) {
+        if ((rc = ws.fuse.ensure(c, FUSE_BYTES / 8))) return rc;
+        HIPC(c, hipMemsetAsync(ws.fuse, 0, FUSE_BYTES, st));
+    }
+    return 0;
+}
+
+// The learn stage (neigh.hip) on stream st with workspace W: one launch.
+int neigh_learn_enqueue(udpdk_gpu_ctx *c, NeighLearnWs &W, hipStream_t st, const udpdk_neigh_cfg_t *cfg,
+                        const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, uint32_t now)
+{
+    const uint32_t nb = ceil_div(bt->n, NL_TILE);
+    int rc = neigh_ws(c, W, st, bt->n, NL_TILE, NL_ROW);
+    if (rc) return rc;
+    if (!bt->n) {
+        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(NeighLearnResult), st));
+        W.res.ran = true;
+        return 0;
+    }
+    NeighLearnArgs a;
+    a.frames = bt->frames_dev;
+    a.offset = bt->offset_dev;
+    a.length = bt->length_dev;
+    a.meta = meta_dev;
+    a.tab = c->neigh_tab;
+    a.cand = W.cand;
+    a.row = W.row;
+    a.rbase = W.row + (size_t)NL_ROW * nb;
+    a.fuse = W.fuse;
+    a.res = W.res.dev;
+    a.n = bt->n;
+    a.n_blocks = nb;
+    a.frames_bytes = (uint32_t)bt->frames_bytes;
+    a.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+    a.mask = c->neigh_entries - 1u;
+    a.shift = neigh_shift(c->neigh_entries);
+    a.src_ip = cfg->src_ip;
+    mac_words(cfg->src_mac, &a.mac_lo, &a.mac_hi);
+    a.now = now;
+    hipLaunchKernelGGL(neigh_learn, dim3(nb), dim3(NL_BLOCK), 0, st, a);
+    HIPC(c, hipGetLastError());
+    W.res.ran = true;
+    return 0;
+}
+
+void neigh_learn_stats_out(const NeighLearnResult *r, udpdk_neigh_learn_stats_t *st)
+{
+    st->arp = r->c[NL_R_ARP];
+    st->malformed = r->c[NL_R_MALFORMED];
+    st->bad_frame = r->c[NL_R_BAD_FRAME];
+    st->other_op = r->c[NL_R_OTHER_OP];
+    st->sender_bad = r->c[NL_R_SENDER_BAD];
+    st->updated = r->o[NL_O_UPDATED];
+    st->refreshed = r->o[NL_O_REFRESHED];
+    st->static_kept = r->o[NL_O_STATIC_KEPT];
+    st->created = r->o[NL_O_CREATED];
+    st->full = r->o[NL_O_FULL];
+    st->ignored = r->o[NL_O_IGNORED];
+}
+
+} // namespace
+
+int udpdk_gpu_neigh_create(udpdk_gpu_ctx *c, uint32_t entries)
+{
+    if (!c || entries < 8u || entries > UDPDK_NEIGH_MAX_ENTRIES || (entries & (entries - 1u))) return -EINVAL;
+    HIPC(c, hipSetDevice(c->device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    c->neigh_entries = 0;
+    c->neigh_tab.release();
+    if ((rc = c->neigh_tab.ensure(c, (size_t)entries * 4u))) return rc;
+    HIPC(c, hipMemset(c->neigh_tab, 0, (size_t)entries * 16u));
+    c->neigh_entries = entries;
+    return 0;
+}
+
+int udpdk_gpu_neigh_set(udpdk_gpu_ctx *c, const udpdk_neigh_entry_t *e, uint32_t n)
+{
+    if (!c || (!e && n)) return -EINVAL;
+    for (uint32_t i = 0; i < n; ++i)
+        if (e[i].ip == 0u || (e[i].state != UDPDK_NEIGH_STATIC && e[i].state != UDPDK_NEIGH_REACHABLE)) return -EINVAL;
+    std::vector<udpdk_neigh_entry_t> t;
+    int rc = neigh_fetch(c, t), full = 0;
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n && !full; ++i) full = neigh_put(t, e[i]);
+    rc = neigh_store(c, t);
+    return rc ? rc : full;
+}
+
+int udpdk_gpu_neigh_dump(udpdk_gpu_ctx *c, udpdk_neigh_entry_t *out, uint32_t cap, uint32_t *n)
+{
+    if (!c || !n || (!out && cap)) return -EINVAL;
+    std::vector<udpdk_neigh_entry_t> t;
+    const int rc = neigh_fetch(c, t);
+    if (rc) return rc;
+    uint32_t k = 0;
+    for (const udpdk_neigh_entry_t &e : t) {
+        if (e.ip == 0u) continue;
+        if (k < cap) out[k] = e;
+        ++k;
+    }
+    *n = k;
+    return k > cap ? -ENOSPC : 0;
+}
+
+int udpdk_gpu_neigh_flush(udpdk_gpu_ctx *c, int keep_static)
+{
+    std::vector<udpdk_neigh_entry_t> t;
+    int rc = neigh_fetch(c, t);
+    if (rc) return rc;
+    // (the kept entries are put back by key: a probe sequence ends at the first empty slot)
+    std::vector<udpdk_neigh_entry_t> u(t.size(), udpdk_neigh_entry_t{});
+    if (keep_static)
+        for (const udpdk_neigh_entry_t &e : t)
+            if (e.ip != 0u && e.state == UDPDK_NEIGH_STATIC) (void)neigh_put(u, e);
+    return neigh_store(c, u);
+}
+
+int udpdk_gpu_neigh_geometry(uint32_t *learn_frames_per_block, uint32_t *resolve_per_block)
+{
+    if (!learn_frames_per_block || !resolve_per_block) return -EINVAL;
+    *learn_frames_per_block = NL_TILE;
+    *resolve_per_block = NR_TILE;
+    return 0;
+}
+
+int udpdk_gpu_neigh_class(const udpdk_neigh_cfg_t *cfg, uint32_t dst_ip, uint32_t *next_hop, uint8_t *mac_out)
+{
+    if (!cfg || !next_hop || !mac_out) return -EINVAL;
+    uint32_t s_lo, s_hi, lo, hi;
+    mac_words(cfg->src_mac, &s_lo, &s_hi);
+    const uint32_t cls = neigh_class(cfg->src_ip, cfg->netmask, cfg->gateway, s_lo, s_hi, dst_ip, next_hop, &lo, &hi);
+    memcpy(mac_out, &lo, 4);
+    memcpy(mac_out + 4, &hi, 2);
+    return (int)cls;
+}
+
+int udpdk_gpu_neigh_learn(udpdk_gpu_ctx *c, const udpdk_neigh_cfg_t *cfg, const udpdk_rx_batch_t *bt,
+                          const uint32_t *meta_dev, uint32_t now)
+{
+    int rc = neigh_learn_check(c, cfg, bt, meta_dev);
+    if (rc) return rc;
+    if ((rc = on_ctx_stream(c))) return rc;
+    return neigh_learn_enqueue(c, c->nlearn, c->stream, cfg, bt, meta_dev, now);
+}
+
+int udpdk_gpu_neigh_learn_stats(udpdk_gpu_ctx *c, udpdk_neigh_learn_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    const int rc = ctx_result(c, c->nlearn.res);
+    if (!rc) neigh_learn_stats_out(c->nlearn.res.host, st);
+    return rc;
+}
+
+int udpdk_gpu_pipe_neigh_learn(udpdk_gpu_ctx *c, int pipe, const udpdk_neigh_cfg_t *cfg,
+                               const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, uint32_t now)
+{
+    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    int rc = neigh_learn_check(c, cfg, bt, meta_dev);
+    if (rc) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    Pipe &P = c->pipes[pipe];
+    if (!P.stream) return -EINVAL;
+    P.dirty = true;
+    if ((rc = neigh_learn_enqueue(c, P.nlearn, P.stream, cfg, bt, meta_dev, now))) return rc;
+    // the counts follow on the pipe's stream, read after udpdk_gpu_pipe_wait
+    return P.nlearn.res.enqueue_fetch(c, P.stream);
+}
+
+int udpdk_gpu_pipe_neigh_learn_stats(udpdk_gpu_ctx *c, int pipe, udpdk_neigh_learn_stats_t *st)
+{
+    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    const ResultSlot<NeighLearnResult> &R = c->pipes[pipe].nlearn.res;
+    if (!R.ran) return -ENOENT;
+    neigh_learn_stats_out(R.host, st);
+    return 0;
+}
+
+int udpdk_gpu_neigh_resolve(udpdk_gpu_ctx *c, const udpdk_neigh_cfg_t *cfg, const uint32_t *dst_ip_dev,
+                            const int32_t *sockfd_dev, uint32_t n, uint32_t now, const udpdk_neigh_out_t *o)
+{
+    int rc = neigh_cfg_check(c, cfg);
+    if (rc) return rc;
+    if (!dst_ip_dev || !sockfd_dev || !o || !o->dmac_dev || !o->sockfd_out_dev || !o->state_dev) return -EINVAL;
+    if (o->req_cap && (!o->req_dev || !o->req_origin_dev)) return -EINVAL;
+    if (((uintptr_t)o->dmac_dev & 7u) || ((uintptr_t)o->req_dev & 15u)) return -EINVAL;
+    if ((rc = on_ctx_stream(c))) return rc;
+    NeighResolveWs &W = c->nresolve;
+    const uint32_t nb = ceil_div(n, NR_TILE);
+    if ((rc = neigh_ws(c, W, c->stream, n, NR_TILE, NR_ROW))) return rc;
+    if (!n) {
+        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(NeighResolveResult), c->stream));
+        W.res.ran = true;
+        return 0;
+    }
+    NeighResolveArgs a;
+    a.dst_ip = dst_ip_dev;
+    a.sockfd = sockfd_dev;
+    a.dmac = o->dmac_dev;
+    a.sockfd_out = o->sockfd_out_dev;
+    a.state = o->state_dev;
+    a.req = o->req_dev;
+    a.req_origin = o->req_origin_dev;
+    a.tab = c->neigh_tab;
+    a.cand = W.cand;
+    a.row = W.row;
+    a.rbase = W.row + (size_t)NR_ROW * nb;
+    a.fuse = W.fuse;
+    a.res = W.res.dev;
+    a.n = n;
+    a.n_blocks = nb;
+    a.req_cap = o->req_cap;
+    a.mask = c->neigh_entries - 1u;
+    a.shift = neigh_shift(c->neigh_entries);
+    a.src_ip = cfg->src_ip;
+    a.netmask = cfg->netmask;
+    a.gateway = cfg->gateway;
+    mac_words(cfg->src_mac, &a.mac_lo, &a.mac_hi);
+    mac_words(cfg->fallback_mac, &a.fb_lo, &a.fb_hi);
+    a.ttl_ms = cfg->ttl_ms;
+    a.retrans_ms = std::max(cfg->retrans_ms, 1u);
+    a.fallback = (cfg->flags & UDPDK_NEIGH_FALLBACK) ? 1u : 0u;
+    a.now = now;
+    hipLaunchKernelGGL(neigh_resolve, dim3(nb), dim3(NR_BLOCK), 0, c->stream, a);
+    HIPC(c, hipGetLastError());
+    W.res.ran = true;
+    return 0;
+}
+
+int udpdk_gpu_neigh_resolve_stats(udpdk_gpu_ctx *c, udpdk_neigh_resolve_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    const int rc = ctx_result(c, c->nresolve.res);
+    if (rc) return rc;
+    const NeighResolveResult *r = c->nresolve.res.host;
+    st->skipped = r->c[NR_R_SKIPPED];
+    st->bcast = r->c[NR_R_BCAST];
+    st->mcast = r->c[NR_R_MCAST];
+    st->no_route = r->c[NR_R_NO_ROUTE];
+    st->self = r->c[NR_R_SELF];
+    st->hit = r->c[NR_R_HIT];
+    st->expired = r->o[NR_O_EXPIRED];
+    st->incomplete = r->o[NR_O_INCOMPLETE];
+    st->inserted = r->o[NR_O_INSERTED];
+    st->table_full = r->o[NR_O_TABLE_FULL];
+    st->fallback = r->fallback;
+    st->unresolved = r->unresolved;
+    st->requests = r->requests;
+    st->no_room = r->no_room;
+    return st->no_room ? -ENOSPC : 0;
 }
 
 #ifdef UDPDK_STAMPS
