@@ -376,6 +376,52 @@ typedef struct {
 } udpdk_arp_counts_t;
 int udpdk_arp_counts(udpdk_arp_counts_t *counts);
 
+/* Multicast (ini: [gpu] mcast = 0 | 1; default 0: as in the reference, which has no multicast, a
+ * datagram to 239.1.2.3:5000 lands in every socket bound to ANY:5000, no IGMP is sent and a query
+ * ends as NOT_UDP).
+ *   udpdk_setsockopt(s, IPPROTO_IP, IP_ADD_MEMBERSHIP | IP_DROP_MEMBERSHIP, struct ip_mreq | struct
+ *   ip_mreqn) records a membership whether or not the switch is on. imr_interface (imr_address) must
+ *   be INADDR_ANY or our address and an interface index 0, else ENODEV; a group outside 224.0.0.0/4:
+ *   EINVAL; a second join of the same group on the socket: EADDRINUSE; a drop without a join:
+ *   EADDRNOTAVAIL; more than 20 groups on one socket: ENOBUFS (Linux's igmp_max_memberships); any
+ *   other IPPROTO_IP option: ENOPROTOOPT. udpdk_close drops the socket's groups.
+ * Membership is PER SOCKET, which is Linux with IP_MULTICAST_ALL = 0 and not Linux's default: a
+ * socket receives a group only if it joined the group itself, not because another socket of the
+ * host did.
+ * With the switch on
+ *  - udpdk_poll_rx runs the membership filter (udpdk_gpu_rx_mcast, udpdk_gpu.h) as the last
+ *    lane-removal stage of every RX call, the pass over reassembled datagrams included: a socket
+ *    bound to INADDR_ANY or to a group address keeps a multicast datagram only if it joined the
+ *    datagram's group; unicast and 255.255.255.255 pass, and a socket bound to a specific unicast
+ *    address is not looked at. udpdk_rx_not_member counts what the filter removed. The tables are
+ *    uploaded again whenever a membership or the bind table changed.
+ *  - udpdk_poll_rx runs udpdk_gpu_igmp_reply on every staged batch whose RX counters show a frame
+ *    that is IPv4 but not UDP, while at least one group is joined, before the ICMP stage: a general
+ *    query is answered with one IGMPv2 report per joined group, a group-specific query with that
+ *    group's. The reports, 46 bytes each, go onto the host queue of the ICMP answers, so
+ *    udpdk_tx_drain emits them before the socket datagrams and udpdk_tx_pending counts them. At most
+ *    4096 distinct groups are answered for.
+ *  - the first join of a group queues one unsolicited report, the last drop of a group (udpdk_close
+ *    included) one leave to 224.0.0.2, and turning the switch on one report per group already
+ *    joined. 224.0.0.1 is never reported. Nothing is sent without a source address.
+ * Not done: IGMPv3 and source filters; report suppression and the random response delay (a report
+ * leaves with the next drain); the second unsolicited report; IP_MULTICAST_TTL, IP_MULTICAST_LOOP and
+ * IP_MULTICAST_IF; sharded polls (there on = 1 gives -1 with ENOTSUP and udpdk_init fails on such
+ * an ini, as for udpdk_config_arp); udpdk_poll_echo. Returns the value in force before the call; a
+ * negative argument only reads it; above 1: -1, EINVAL. */
+int udpdk_config_mcast(int on);
+/* Session sums, like udpdk_arp_counts: the batches or chunks the IGMP stage ran on (scanned), the
+ * device stage's counts (udpdk_igmp_stats_t without no_room and bad_frame), the memberships added
+ * and dropped (joins, leaves; counted with the switch off too) and the reports and leaves queued.
+ * udpdk_host_reset zeroes them. */
+typedef struct {
+    uint64_t scanned, igmp, malformed, bad_cksum, other_type, bad_dst, general, not_member, specific, reports,
+             joins, leaves, reports_sent, leaves_sent;
+} udpdk_mcast_counts_t;
+int udpdk_mcast_counts(udpdk_mcast_counts_t *counts);
+/* Deliveries the membership filter removed, summed over the session like udpdk_rx_refused. */
+uint64_t udpdk_rx_not_member(void);
+
 /* Neighbours (ini: [gpu] neigh = 0 | 1 | fallback; default 0: as in the reference, every frame goes to
  * the [port0_dst] MAC). With the switch on the main context keeps a neighbour table (udpdk_gpu.h; ini:
  * [gpu] neigh_entries, default 1024; neigh_ttl_ms, default 30000; neigh_retrans_ms, default 1000), and

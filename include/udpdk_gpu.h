@@ -60,7 +60,10 @@ extern "C" {
  *    udpdk_gpu_pipe_arp_reply / udpdk_gpu_pipe_arp_stats were added)
  *    (still 3: udpdk_gpu_neigh_create / _set / _dump / _flush / _learn / _learn_stats / _resolve /
  *    _resolve_stats / _geometry / _class, udpdk_gpu_pipe_neigh_learn / _learn_stats and
- *    udpdk_gpu_tx_build_neigh were added) */
+ *    udpdk_gpu_tx_build_neigh were added)
+ *    (still 3: udpdk_gpu_rx_mcast_select / udpdk_gpu_rx_mcast / udpdk_gpu_rx_mcast_stats /
+ *    udpdk_gpu_rx_mcast_removed / udpdk_gpu_mcast_table_build, udpdk_gpu_igmp_reply / _stats /
+ *    _geometry and udpdk_gpu_pipe_igmp_reply / _stats were added) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -497,6 +500,93 @@ int udpdk_gpu_rx_peer_stats(udpdk_gpu_ctx *ctx, udpdk_rx_peer_stats_t *stats);
 /* Poller internals, the sibling of udpdk_gpu_rx_removed: the lane entries the sticky peer filter
  * removed in the call whose results were last written to *stats (-ENOENT when no call's were). */
 int udpdk_gpu_rx_peer_removed(udpdk_gpu_ctx *ctx, const udpdk_rx_stats_t *stats, uint32_t *refused);
+
+/* ---------------------------------------------------------------------------------------------
+ * RX multicast membership filter: a socket's lane keeps a multicast datagram only if the socket
+ * joined the datagram's group (IP_ADD_MEMBERSHIP, udpdk_api.h). udpdk_gpu_rx matches a frame's
+ * destination against a binding's address or INADDR_ANY, so without this stage a datagram to
+ * 239.1.2.3:5000 lands in every ANY:5000 socket. The reference has no multicast; the rule is RFC
+ * 1112's host group model with per-socket membership (Linux with IP_MULTICAST_ALL = 0). Off by
+ * default: then udpdk_gpu_rx enqueues what it always did.
+ *
+ * The uploaded snapshot must have lane_mask == 0xFFFFFFFF (a lane is a sockfd). lane_mc is a
+ * uint8[n_lanes] table. D = min(lane_off[n_lanes], lane_cap). Entry p of lane l with frame
+ * i = lane_pkt[p] is handled by the first rule that applies:
+ *   - i >= n: removed (bad_index); no descriptor or frame byte of it is read.
+ *   - lane_mc[l] == 0: kept; no descriptor and no frame byte is read for the entry. (The socket
+ *     layer clears lane_mc for sockets bound to a specific non-multicast address: the demux already
+ *     proved the destination equals that address.)
+ *   - length[i] < 42 or offset[i] + length[i] > frames_bytes (summed in 64 bits): removed
+ *     (bad_frame); no frame byte is read.
+ *   - dst = the raw u32 at frame bytes 30-33. If its first byte (dst & 0xFF) is outside 224..239 the
+ *     entry is kept: unicast and 255.255.255.255.
+ *   - otherwise kept iff (dst, l) is in the membership table (member), else removed (not_member).
+ *   - The rule is per entry: a frame that fans out to a joined and an unjoined lane stays in the
+ *     first only.
+ *   - The output is the drop filter's: a stable compaction, lane_off_out[l] = kept entries before
+ *     min(lane_off[l], D), nothing past lane_cap read, nothing past out_cap written.
+ * meta is never read (lanes->meta_dev may be NULL) or rewritten.
+ *
+ * The membership table is read-only on the device: the caller builds it (udpdk_gpu_mcast_table_build)
+ * and the stage never writes it. `slots` records, slots a power of two in 2..2^20; group == 0 marks
+ * an empty slot. Open addressing, linear probing: the probe of (group, lane) starts at index
+ * h >> (32 - log2(slots)), h = (group ^ (lane * 0x9E3779B1u)) * 0x85EBCA6Bu in uint32 arithmetic,
+ * steps by one (wrapping past the last slot) and ends at a match, at an empty slot, or after
+ * `slots` probes: a table with no empty slot is valid and its probes are bounded.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t group; uint32_t lane; } udpdk_mcast_member_t;   /* raw group; 8 bytes */
+
+/* Host only, pure: the table of members[n] in table_out[slots], inserted in the caller's order
+ * (every slot is written: the ones not taken are zeroed). -EINVAL: a NULL pointer (members may be
+ * NULL when n == 0), slots not a power of two in 2..2^20, a member with group == 0, a pair given
+ * twice. -ENOSPC: n > slots. */
+int udpdk_gpu_mcast_table_build(const udpdk_mcast_member_t *members, uint32_t n,
+                                udpdk_mcast_member_t *table_out, uint32_t slots);
+
+/* The filter as an explicit call on any lane set (lanes->n == batch->n): out of place, async on the
+ * context stream. lane_mc_dev is [lanes->n_lanes]; table_dev is [slots], 8-byte aligned. An
+ * all-zero lane_mc is a valid identity copy (only entries >= n are removed). -EINVAL with nothing
+ * enqueued: the cases of udpdk_gpu_rx_peer_select (a NULL pointer, n_lanes outside
+ * 1..UDPDK_GPU_MAX_LANES, no snapshot uploaded or one with lane_mask != 0xFFFFFFFF, outputs that
+ * overlap the input lanes, lanes->n != batch->n, table_dev not 8-byte aligned), and slots not a
+ * power of two in 2..2^20. The frames buffer keeps the tailroom contract of udpdk_gpu_rx. */
+int udpdk_gpu_rx_mcast_select(udpdk_gpu_ctx *ctx, const udpdk_rx_batch_t *batch,
+                              const udpdk_rx_lanes_t *lanes, const uint8_t *lane_mc_dev,
+                              const udpdk_mcast_member_t *table_dev, uint32_t slots,
+                              uint32_t *lane_off_out_dev, uint32_t *lane_pkt_out_dev, uint32_t out_cap);
+/* Sticky mode: uploads lane_mc_host[n_lanes] (n_lanes <= the context's max_lanes; lanes past it are
+ * exempt) and the table of members_host[n_members] (n_members <= 2^19; every member's lane <
+ * n_lanes), built with slots = the smallest power of two >= 2 * n_members (minimum 2). NULL
+ * lane_mc_host or n_lanes == 0 turns the stage off (default: no stage is enqueued); members_host may
+ * be NULL when n_members == 0 (then checked lanes lose every multicast entry). -EINVAL for a pair
+ * given twice, a group == 0, a lane >= n_lanes. Synchronises the context. Afterwards every
+ * udpdk_gpu_rx / udpdk_gpu_rx_host / udpdk_gpu_rx_host_async / udpdk_gpu_pipe_rx_host call on this
+ * context filters its lanes, on the call's own stream, before anything reads them. The stage runs
+ * after the drop filter, the balance and the peer filter; all four are per-entry predicates that do
+ * not depend on what else the lanes hold, so they commute. A call under a snapshot with lane_mask
+ * != 0xFFFFFFFF returns -EINVAL.
+ *   - udpdk_rx_stats_t: counters[] (UDPDK_C_DELIVERIES too) stay classify's; deliveries becomes
+ *     the kept count, so it still equals lane_off[n_lanes]; overflow and -ENOSPC are still decided
+ *     by the pre-stage total against lane_cap. */
+int udpdk_gpu_rx_mcast(udpdk_gpu_ctx *ctx, const uint8_t *lane_mc_host, uint32_t n_lanes,
+                       const udpdk_mcast_member_t *members_host, uint32_t n_members);
+
+typedef struct {
+    uint32_t kept, removed;
+    uint32_t member;       /* multicast entries of checked lanes kept: the lane joined the group  */
+    uint32_t not_member;   /* ... removed: it did not                                             */
+    uint32_t bad_frame;    /* entries of checked lanes whose frame is shorter than 42 bytes or out
+                              of range: not read                                                  */
+    uint32_t bad_index;    /* entries >= n: removed, nothing of theirs read                       */
+    uint32_t truncated;    /* input lane_off[n_lanes] > lane_cap: only the first lane_cap seen    */
+} udpdk_rx_mcast_stats_t;
+/* Of the last membership filter run on the context (explicit or sticky; -ENOENT when there was
+ * none). Synchronises. -ENOSPC if kept > out_cap. The launches are not event-timed. */
+int udpdk_gpu_rx_mcast_stats(udpdk_gpu_ctx *ctx, udpdk_rx_mcast_stats_t *stats);
+/* Poller internals, the sibling of udpdk_gpu_rx_peer_removed: the lane entries the sticky
+ * membership filter removed in the call whose results were last written to *stats (-ENOENT when no
+ * call's were). */
+int udpdk_gpu_rx_mcast_removed(udpdk_gpu_ctx *ctx, const udpdk_rx_stats_t *stats, uint32_t *not_member);
 
 /* ---------------------------------------------------------------------------------------------
  * RX payload delivery: the batch form of udpdk_recvfrom (udpdk_syscall.c:401-488) over the lane
@@ -1032,6 +1122,101 @@ int udpdk_gpu_pipe_arp_reply(udpdk_gpu_ctx *ctx, int pipe, const udpdk_tx_config
                              const udpdk_rx_batch_t *batch, const uint32_t *meta_dev,
                              const udpdk_arp_out_t *out);
 int udpdk_gpu_pipe_arp_stats(udpdk_gpu_ctx *ctx, int pipe, udpdk_arp_stats_t *stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * IGMPv2 on the device: membership reports in answer to membership queries (RFC 2236), so that a
+ * switch with IGMP snooping or a multicast router keeps forwarding the groups the stack joined. The
+ * reference has no IGMP: a query ends as UDPDK_V_NOT_UDP and nothing looks at it again. This optional
+ * stage after udpdk_gpu_rx answers from what is already in device memory (the verdict words, the
+ * staged frames) and the caller's list of joined groups. Off unless called.
+ *
+ * All addresses are raw. groups_dev[n_groups] holds distinct group addresses in the caller's order,
+ * n_groups <= UDPDK_IGMP_MAX_GROUPS. The first failing step decides the single counter a frame
+ * lands in.
+ *   1. Candidate by meta: verdict UDPDK_V_NOT_UDP. For any other frame no descriptor and no frame
+ *      byte is read, so a batch of UDP costs the read of meta.
+ *   2. Frame gate: length[i] >= 34 and offset[i] + length[i] <= frames_bytes (64 bits), else the
+ *      candidate counts as bad_frame and no frame byte is read.
+ *   3. Byte 23 == 2 (IGMP), else the frame is counted nowhere (ICMP, TCP, ...). Then igmp++.
+ *   4. IHL = the low nibble of byte 14, 5..15; the IPv4 total length (bytes 16-17) >= 4 IHL + 8;
+ *      14 + total length <= length[i]; the header checksum over all 4 IHL bytes verifies (the verdict
+ *      word's IP bit covers 20 bytes only, and a query carries Router Alert: IHL 6). Else malformed.
+ *   5. The IGMP message is the total length - 4 IHL bytes at 14 + 4 IHL: 8 (v1, v2), 12 or more
+ *      (v3), at most what the 16-bit total length allows. Its RFC 1071 checksum over the whole
+ *      message verifies, an odd length padded with a zero byte. Else bad_cksum.
+ *   6. The type, message byte 0, == 0x11 (membership query), else other_type: the reports and
+ *      leaves of others (0x12, 0x16, 0x17, 0x22) and anything else.
+ *   7. The group, message bytes 4-7. Zero: a general query, whose destination (bytes 30-33) must be
+ *      224.0.0.1, else bad_dst; then general. Non-zero: a group-specific query, whose destination
+ *      must equal the group, else bad_dst; a group that is not in groups_dev: not_member; then
+ *      specific.
+ *   8. The max response time is ignored: the answer leaves with the caller's next transmission,
+ *      inside any response window; there is no random delay and no suppression on hearing another
+ *      member's report. A v1 or v3 query is answered as a v2 query (RFC 2236 section 2.5).
+ *
+ * The answer set is a bitmap over groups_dev: a general query sets every group except 224.0.0.1, a
+ * specific query its own group. Report r is for the r-th set group in index order, so each group
+ * gets at most one report per call however many queries ask for it. It is written iff
+ * r < max_reports, with group_index[r] the group's index in groups_dev, into the
+ * UDPDK_IGMP_SLOT_BYTES slot at 64 r (g = the group's four address bytes):
+ *   bytes 0-5    01 00 5e, g[1] & 0x7f, g[2], g[3]
+ *         6-11   cfg->src_mac
+ *         12-13  08 00
+ *         14-37  46 c0 00 20 00 00 40 00 01 02 <checksum> <cfg->src_ip> <g> 94 04 00 00
+ *         38-45  16 00 <checksum> <g>
+ *         46-63  zero
+ * Slots and index entries of r >= reports are not written; the groups cut are a tail (no_room).
+ * cfg->dst_mac is not used.
+ *
+ * Asynchronous on the context stream; joins the pipes as udpdk_gpu_arp_reply does. -EINVAL with
+ * nothing enqueued: a NULL pointer (groups_dev may be NULL when n_groups == 0), cfg->src_ip == 0,
+ * n_groups > UDPDK_IGMP_MAX_GROUPS, frames_bytes >= 2^32, out->frames_dev not 16-byte aligned, an
+ * output that overlaps the frame buffer. n == 0 returns 0 with all counts zero. The frames buffer
+ * keeps the tailroom contract of udpdk_gpu_rx. meta, frames and groups are read and never written. No
+ * snapshot is needed. The launch is not event-timed. One launch: its last workgroup to finish
+ * writes the reports.
+ * ------------------------------------------------------------------------------------------- */
+#define UDPDK_IGMP_FRAME_BYTES 46u  /* 14 Ethernet + 24 IPv4 with Router Alert + 8 IGMP         */
+#define UDPDK_IGMP_SLOT_BYTES  64u  /* device output stride: the frame, then 18 zero bytes      */
+#define UDPDK_IGMP_MAX_GROUPS  4096u
+
+typedef struct {
+    uint8_t  *frames_dev;       /* [max_reports * 64], 16-byte aligned; report r at 64 * r      */
+    uint32_t *group_index_dev;  /* [max_reports] index in groups_dev of the group of report r   */
+    uint32_t  max_reports;
+} udpdk_igmp_out_t;
+
+typedef struct {
+    uint32_t igmp;        /* candidates past the frame gate with protocol 2                     */
+    uint32_t malformed;   /* ... whose IHL, total length or header checksum is wrong            */
+    uint32_t bad_cksum;   /* ... whose IGMP checksum fails                                      */
+    uint32_t other_type;  /* ... of a type other than 0x11                                      */
+    uint32_t bad_dst;     /* queries sent to an address that does not go with their group field */
+    uint32_t general;     /* general queries answered                                           */
+    uint32_t not_member;  /* group-specific queries for a group that is not in groups_dev       */
+    uint32_t specific;    /* group-specific queries answered                                    */
+    uint32_t reports;     /* written: min(groups to report, max_reports)                        */
+    uint32_t no_room;     /* groups to report - reports (a tail in index order)                 */
+    uint32_t bad_frame;   /* candidate by meta, but length < 34 or out of range: not read       */
+} udpdk_igmp_stats_t;
+
+int udpdk_gpu_igmp_reply(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg,
+                         const udpdk_rx_batch_t *batch, const uint32_t *meta_dev,
+                         const uint32_t *groups_dev, uint32_t n_groups, const udpdk_igmp_out_t *out);
+/* Of the last udpdk_gpu_igmp_reply on the context (-ENOENT when there was none). Synchronises.
+ * -ENOSPC when no_room > 0. */
+int udpdk_gpu_igmp_stats(udpdk_gpu_ctx *ctx, udpdk_igmp_stats_t *stats);
+/* Frames per workgroup of the kernel and the workgroup count for n frames (host only, like
+ * udpdk_gpu_arp_geometry). */
+int udpdk_gpu_igmp_geometry(uint32_t n, uint32_t *frames_per_block, uint32_t *n_blocks);
+/* Poller internals: the same stage on pipe `pipe`'s stream (1 .. 3) with that pipe's workspace and
+ * no joins, like udpdk_gpu_pipe_arp_reply; the counts are copied to pinned memory on the same
+ * stream. udpdk_gpu_pipe_igmp_stats reads them without synchronising: they are those of the pipe's
+ * last stage once udpdk_gpu_pipe_wait has returned (-ENOENT: the pipe never ran one; -ENOSPC as above). */
+int udpdk_gpu_pipe_igmp_reply(udpdk_gpu_ctx *ctx, int pipe, const udpdk_tx_config_t *cfg,
+                              const udpdk_rx_batch_t *batch, const uint32_t *meta_dev,
+                              const uint32_t *groups_dev, uint32_t n_groups, const udpdk_igmp_out_t *out);
+int udpdk_gpu_pipe_igmp_stats(udpdk_gpu_ctx *ctx, int pipe, udpdk_igmp_stats_t *stats);
 
 /* ---------------------------------------------------------------------------------------------
  * Neighbour cache on the device: a table of on-link IPv4 addresses and their MACs, learned from the

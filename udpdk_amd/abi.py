@@ -109,6 +109,16 @@ class RxPeerStats(C.Structure):
                 ("bad_frame", C.c_uint32), ("bad_index", C.c_uint32), ("truncated", C.c_uint32)]
 
 
+MCAST_DTYPE = np.dtype([("group", "<u4"), ("lane", "<u4")])   # udpdk_mcast_member_t as a numpy record
+MCAST_MAX_SLOTS = 1 << 20
+
+
+class RxMcastStats(C.Structure):
+    _fields_ = [("kept", C.c_uint32), ("removed", C.c_uint32), ("member", C.c_uint32),
+                ("not_member", C.c_uint32), ("bad_frame", C.c_uint32), ("bad_index", C.c_uint32),
+                ("truncated", C.c_uint32)]
+
+
 BAL_TILE = 1024           # frames per rx_balance_pick workgroup (rx_balance.h)
 BAL_KEEP_ALL = 0xFFFFFFFF
 REUSEPORT_FANOUT, REUSEPORT_BALANCE = 0, 1   # UDPDK_REUSEPORT_*
@@ -222,6 +232,33 @@ ARP_SLOT_BYTES = 64
 class ArpStats(C.Structure):
     """udpdk_arp_stats_t"""
     _fields_ = [(k, C.c_uint32) for k in ARP_STATS]
+
+
+class IgmpOut(C.Structure):
+    """udpdk_igmp_out_t"""
+    _fields_ = [("frames_dev", C.c_void_p), ("group_index_dev", C.c_void_p), ("max_reports", C.c_uint32)]
+
+
+IGMP_STATS = ("igmp", "malformed", "bad_cksum", "other_type", "bad_dst", "general", "not_member", "specific",
+              "reports", "no_room", "bad_frame")
+IGMP_FRAME_BYTES = 46
+IGMP_SLOT_BYTES = 64
+IGMP_MAX_GROUPS = 4096
+
+
+class IgmpStats(C.Structure):
+    """udpdk_igmp_stats_t"""
+    _fields_ = [(k, C.c_uint32) for k in IGMP_STATS]
+
+
+class McastCounts(C.Structure):
+    """udpdk_mcast_counts_t (udpdk_api.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("scanned", "igmp", "malformed", "bad_cksum", "other_type", "bad_dst", "general",
+                                          "not_member", "specific", "reports", "joins", "leaves", "reports_sent",
+                                          "leaves_sent")]
+
+
+IPPROTO_IP, IP_ADD_MEMBERSHIP, IP_DROP_MEMBERSHIP = 0, 35, 36
 
 
 class ArpCounts(C.Structure):
@@ -342,6 +379,12 @@ _PROTOS = {
     "udpdk_gpu_rx_peer": (C.c_int, [_P, _P, C.c_uint32]),
     "udpdk_gpu_rx_peer_stats": (C.c_int, [_P, C.POINTER(RxPeerStats)]),
     "udpdk_gpu_rx_peer_removed": (C.c_int, [_P, C.POINTER(RxStats), C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_mcast_table_build": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
+    "udpdk_gpu_rx_mcast_select": (C.c_int, [_P, C.POINTER(RxBatch), C.POINTER(RxLanes), _P, _P, C.c_uint32, _P, _P,
+                                            C.c_uint32]),
+    "udpdk_gpu_rx_mcast": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32]),
+    "udpdk_gpu_rx_mcast_stats": (C.c_int, [_P, C.POINTER(RxMcastStats)]),
+    "udpdk_gpu_rx_mcast_removed": (C.c_int, [_P, C.POINTER(RxStats), C.POINTER(C.c_uint32)]),
     "udpdk_gpu_rx_gather": (C.c_int, [_P, C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32,
                                       C.POINTER(RxGather)]),
     "udpdk_gpu_rx_gather_packed": (C.c_int, [_P, C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32, _P,
@@ -383,6 +426,13 @@ _PROTOS = {
     "udpdk_gpu_pipe_arp_reply": (C.c_int, [_P, C.c_int, C.POINTER(TxConfig), C.POINTER(RxBatch), _P,
                                            C.POINTER(ArpOut)]),
     "udpdk_gpu_pipe_arp_stats": (C.c_int, [_P, C.c_int, C.POINTER(ArpStats)]),
+    "udpdk_gpu_igmp_reply": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(RxBatch), _P, _P, C.c_uint32,
+                                       C.POINTER(IgmpOut)]),
+    "udpdk_gpu_igmp_stats": (C.c_int, [_P, C.POINTER(IgmpStats)]),
+    "udpdk_gpu_igmp_geometry": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_pipe_igmp_reply": (C.c_int, [_P, C.c_int, C.POINTER(TxConfig), C.POINTER(RxBatch), _P, _P, C.c_uint32,
+                                            C.POINTER(IgmpOut)]),
+    "udpdk_gpu_pipe_igmp_stats": (C.c_int, [_P, C.c_int, C.POINTER(IgmpStats)]),
     "udpdk_gpu_neigh_create": (C.c_int, [_P, C.c_uint32]),
     "udpdk_gpu_neigh_set": (C.c_int, [_P, C.POINTER(NeighEntry), C.c_uint32]),
     "udpdk_gpu_neigh_dump": (C.c_int, [_P, C.POINTER(NeighEntry), C.c_uint32, C.POINTER(C.c_uint32)]),
@@ -445,6 +495,9 @@ _PROTOS = {
     "udpdk_config_icmp_errors": (C.c_int, [C.c_int]),
     "udpdk_config_arp": (C.c_int, [C.c_int]),
     "udpdk_arp_announce": (C.c_int, []),
+    "udpdk_config_mcast": (C.c_int, [C.c_int]),
+    "udpdk_mcast_counts": (C.c_int, [C.POINTER(McastCounts)]),
+    "udpdk_rx_not_member": (C.c_uint64, []),
     "udpdk_arp_counts": (C.c_int, [C.POINTER(ArpCounts)]),
     "udpdk_config_neigh": (C.c_int, [C.c_int]),
     "udpdk_neigh_add": (C.c_int, [C.c_uint32, _P]),
@@ -653,6 +706,19 @@ class GpuContext:
         t = np.ascontiguousarray(peers, PEER_DTYPE)
         _check(lib().udpdk_gpu_rx_peer(self.handle, t.ctypes.data_as(C.c_void_p), len(t)), "udpdk_gpu_rx_peer")
 
+    def rx_mcast(self, lane_mc=None, members=None):
+        """Sticky membership filter (udpdk_gpu_rx_mcast): the lanes' checked flags and the (group,
+        lane) members (MCAST_DTYPE) for every later RX call on the context; lane_mc None turns the
+        stage off."""
+        if lane_mc is None or len(lane_mc) == 0:
+            _check(lib().udpdk_gpu_rx_mcast(self.handle, None, 0, None, 0), "udpdk_gpu_rx_mcast")
+            return
+        f = np.ascontiguousarray(lane_mc, np.uint8)
+        m = np.ascontiguousarray(members if members is not None else [], MCAST_DTYPE)
+        _check(lib().udpdk_gpu_rx_mcast(self.handle, f.ctypes.data_as(C.c_void_p), len(f),
+                                        m.ctypes.data_as(C.c_void_p) if len(m) else None, len(m)),
+               "udpdk_gpu_rx_mcast")
+
     def timing(self, every: int):
         """0 = off, N = record kernel events on every Nth udpdk_gpu_rx call."""
         _check(lib().udpdk_gpu_timing_enable(self.handle, int(every)), "timing_enable")
@@ -846,6 +912,57 @@ def rx_peer_run(ctx: GpuContext, b: RxDeviceBatch, lane_off: np.ndarray, lane_pk
                                               C.c_void_p(oo.ptr), C.c_void_p(po.ptr), out_cap),
                "udpdk_gpu_rx_peer_select")
         rc, st = rx_peer_stats(ctx)
+        return (ctx.download(oo, np.uint32, n_lanes + 1), ctx.download(po, np.uint32, out_cap + pad),
+                st, rc)
+    finally:
+        for x in bufs:
+            x.free()
+
+
+def mcast_table_build(members, slots: int) -> tuple[int, np.ndarray]:
+    """udpdk_gpu_mcast_table_build: (rc, table[slots] as MCAST_DTYPE; 0xA5 bytes where the call
+    wrote nothing). Host only."""
+    m = np.ascontiguousarray(members, MCAST_DTYPE)
+    tab = np.full(8 * max(1, min(slots, MCAST_MAX_SLOTS)), 0xA5, np.uint8).view(MCAST_DTYPE)
+    rc = lib().udpdk_gpu_mcast_table_build(m.ctypes.data_as(C.c_void_p) if len(m) else None, len(m),
+                                           tab.ctypes.data_as(C.c_void_p), slots)
+    return rc, tab
+
+
+def rx_mcast_stats(ctx: GpuContext) -> tuple[int, RxMcastStats]:
+    st = RxMcastStats()
+    rc = lib().udpdk_gpu_rx_mcast_stats(ctx.handle, C.byref(st))
+    return rc, st
+
+
+def rx_mcast_run(ctx: GpuContext, b: RxDeviceBatch, lane_off: np.ndarray, lane_pkt: np.ndarray,
+                 lane_mc: np.ndarray, table: np.ndarray, *, n: int | None = None, lane_cap: int | None = None,
+                 out_cap: int | None = None, pad: int = 0, fill: int = 0xA5A5A5A5):
+    """udpdk_gpu_rx_mcast_select over host lane arrays, a table (MCAST_DTYPE[slots]) and a device
+    batch: upload, run, download; rx_peer_run's conventions. Returns (lane_off_out,
+    lane_pkt_out[out_cap + pad], RxMcastStats, rc of udpdk_gpu_rx_mcast_stats)."""
+    lane_off = np.ascontiguousarray(lane_off, np.uint32)
+    lane_pkt = np.ascontiguousarray(lane_pkt, np.uint32)
+    lane_mc = np.ascontiguousarray(lane_mc, np.uint8)
+    table = np.ascontiguousarray(table, MCAST_DTYPE)
+    n = b.n if n is None else n
+    lane_cap = len(lane_pkt) if lane_cap is None else lane_cap
+    out_cap = lane_cap if out_cap is None else out_cap
+    n_lanes = len(lane_off) - 1
+    assert len(lane_mc) >= n_lanes
+    bufs = [ctx.upload(lane_off), ctx.upload(lane_pkt), ctx.upload(lane_mc), ctx.upload(table.view(np.uint8)),
+            ctx.upload(np.full(n_lanes + 1, fill, np.uint32)),
+            ctx.upload(np.full(out_cap + pad, fill, np.uint32))]
+    od, pd, md, td, oo, po = bufs
+    try:
+        bt = RxBatch(b.frames.ptr, b.frames_bytes, b.offset.ptr, b.length.ptr,
+                     b.ptype.ptr if b.ptype is not None else None, n)
+        lanes = RxLanes(None, n, od.ptr, pd.ptr, lane_cap, n_lanes)
+        _check(lib().udpdk_gpu_rx_mcast_select(ctx.handle, C.byref(bt), C.byref(lanes), C.c_void_p(md.ptr),
+                                               C.c_void_p(td.ptr), len(table), C.c_void_p(oo.ptr),
+                                               C.c_void_p(po.ptr), out_cap),
+               "udpdk_gpu_rx_mcast_select")
+        rc, st = rx_mcast_stats(ctx)
         return (ctx.download(oo, np.uint32, n_lanes + 1), ctx.download(po, np.uint32, out_cap + pad),
                 st, rc)
     finally:
@@ -1080,6 +1197,50 @@ def arp_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, meta, *, max_repli
                 "meta": ctx.download(bufs[0], np.uint32, max(1, meta.size))[:meta.size],
                 "slots": ctx.download(bufs[1], np.uint8, ARP_SLOT_BYTES * (max_replies + pad)).reshape(-1, ARP_SLOT_BYTES),
                 "origin": ctx.download(bufs[2], np.uint32, max_replies + pad)}
+    finally:
+        for x in bufs:
+            x.free()
+
+
+def igmp_geometry(n: int) -> tuple[int, int]:
+    """(frames per workgroup, workgroups) of the IGMP kernel for n frames."""
+    e = C.c_uint32()
+    k = C.c_uint32()
+    _check(lib().udpdk_gpu_igmp_geometry(n, C.byref(e), C.byref(k)), "udpdk_gpu_igmp_geometry")
+    return e.value, k.value
+
+
+def igmp_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, meta, groups, *, max_reports=None, n=None,
+             pipe: int = 0, pad: int = 8):
+    """udpdk_gpu_igmp_reply (pipe 0) or udpdk_gpu_pipe_igmp_reply + udpdk_gpu_pipe_wait over host verdict
+    words and raw group addresses. Returns a dict: rc of the call, rc and dict of the stats call, and
+    slots [max_reports + pad, 64] and group_index [max_reports + pad] as downloaded, `pad` elements
+    longer than the call may write and pre-filled with 0xA5 bytes."""
+    meta = np.ascontiguousarray(meta, np.uint32)
+    groups = np.ascontiguousarray(groups, np.uint32)
+    n = b.n if n is None else n
+    max_reports = len(groups) if max_reports is None else max_reports
+    bufs = [ctx.upload(meta if meta.size else np.zeros(1, np.uint32)),
+            ctx.upload(groups if groups.size else np.zeros(1, np.uint32)),
+            ctx.upload(np.full(IGMP_SLOT_BYTES * (max_reports + pad), 0xA5, np.uint8)),
+            ctx.upload(np.full(4 * (max_reports + pad), 0xA5, np.uint8))]
+    try:
+        bt = RxBatch(b.frames.ptr, b.frames_bytes, b.offset.ptr, b.length.ptr,
+                     b.ptype.ptr if b.ptype is not None else None, n)
+        o = IgmpOut(bufs[2].ptr, bufs[3].ptr, max_reports)
+        st = IgmpStats()
+        args = (C.byref(cfg), C.byref(bt), C.c_void_p(bufs[0].ptr), C.c_void_p(bufs[1].ptr), len(groups), C.byref(o))
+        if pipe:
+            rc = lib().udpdk_gpu_pipe_igmp_reply(ctx.handle, pipe, *args)
+            _check(lib().udpdk_gpu_pipe_wait(ctx.handle, pipe), "udpdk_gpu_pipe_wait")
+            src = lib().udpdk_gpu_pipe_igmp_stats(ctx.handle, pipe, C.byref(st))
+        else:
+            rc = lib().udpdk_gpu_igmp_reply(ctx.handle, *args)
+            src = lib().udpdk_gpu_igmp_stats(ctx.handle, C.byref(st))
+        ctx.sync()
+        return {"rc": rc, "stats_rc": src, "stats": {k: getattr(st, k) for k in IGMP_STATS},
+                "slots": ctx.download(bufs[2], np.uint8, IGMP_SLOT_BYTES * (max_reports + pad)).reshape(-1, IGMP_SLOT_BYTES),
+                "group_index": ctx.download(bufs[3], np.uint32, max_reports + pad)}
     finally:
         for x in bufs:
             x.free()
@@ -1491,6 +1652,33 @@ class HostApi:
 
     def arp_announce(self) -> int:
         return self.L.udpdk_arp_announce()
+
+    def config_mcast(self, on: int) -> int:
+        """The membership filter and IGMP from udpdk_poll_rx (udpdk_config_mcast): returns the previous
+        setting; a negative `on` only reads it."""
+        return self.L.udpdk_config_mcast(int(on))
+
+    def membership(self, s, opt: int, group: str | int, iface: str | int = 0, ifindex: int | None = None) -> int:
+        """udpdk_setsockopt(s, IPPROTO_IP, opt, struct ip_mreq), or struct ip_mreqn when ifindex is given."""
+        v = struct.pack("<II", raw_ip(group) if isinstance(group, str) else group,
+                        raw_ip(iface) if isinstance(iface, str) else iface)
+        if ifindex is not None:
+            v += struct.pack("<i", ifindex)
+        return self.L.udpdk_setsockopt(s, IPPROTO_IP, opt, C.create_string_buffer(v, len(v)), len(v))
+
+    def join(self, s, group, iface=0) -> int:
+        return self.membership(s, IP_ADD_MEMBERSHIP, group, iface)
+
+    def leave(self, s, group, iface=0) -> int:
+        return self.membership(s, IP_DROP_MEMBERSHIP, group, iface)
+
+    def mcast_counts(self) -> dict:
+        c = McastCounts()
+        _check(self.L.udpdk_mcast_counts(C.byref(c)), "udpdk_mcast_counts")
+        return {k: int(getattr(c, k)) for k, _ in McastCounts._fields_}
+
+    def rx_not_member(self) -> int:
+        return int(self.L.udpdk_rx_not_member())
 
     def arp_counts(self) -> ArpCounts:
         c = ArpCounts()

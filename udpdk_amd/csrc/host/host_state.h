@@ -27,6 +27,7 @@
 #define H_MAX_WORKERS    31      /* poll worker threads beyond the caller's ([gpu] poll_threads) */
 #define H_POLL_THREADS_DEFAULT 8
 #define H_UDP_MAX_PAYLOAD 65507  /* 65535 - 20 - 8: the largest datagram fragmentation can carry */
+#define H_MCAST_MAX      20      /* groups a socket can join: Linux's igmp_max_memberships default */
 
 /* A pinned host slab of gathered payloads: one per rx_gather of a poll. Ring entries point into
  * it; the last recvfrom of its datagrams returns it to the pool (the mbuf pool's role). */
@@ -93,6 +94,8 @@ struct h_slot {                  /* exch_slot_info (udpdk_types.h:40-47) + bind 
     uint16_t peer_port;          /* raw */
     uint32_t peer_ip;            /* raw */
     atomic_int so_error;         /* pending ICMP error (udpdk_sock_error_post): an errno, 0 = none     */
+    uint8_t  n_mc;               /* groups joined (IP_ADD_MEMBERSHIP), raw addresses, in no order       */
+    uint32_t mc_group[H_MCAST_MAX];
     struct h_ring rx;
     struct h_txq  tx;
 };
@@ -285,6 +288,20 @@ struct h_state {
     udpdk_peer_t peer_up[UDPDK_MAX_SOCKETS];
     void     *ie_d, *ie_h;
     uint64_t  ie_d_cap, ie_h_cap;
+    /* Multicast (mcast.c): [gpu] mcast / udpdk_config_mcast (0: a poll and a drain enqueue what they
+     * always did; memberships are recorded either way), whether the main context holds the membership
+     * filter and from which versions of the memberships and the snapshot it was built, the session's
+     * counts (mcast_counts under tx_lock; the reports and leaves share the ICMP queue); work buffers: the
+     * host lists a poll uploads (members, then the distinct groups, then the lanes' flags), the device
+     * copy of the distinct groups, the IGMP stage's device slots + group indices and their pinned
+     * readback */
+    uint32_t  mcast_on, mcast_applied;
+    uint64_t  mcast_version, mcast_version_applied, mcast_snap_version;
+    uint64_t  rx_not_member;     /* deliveries the membership filter removed (udpdk_rx_not_member)   */
+    udpdk_mcast_counts_t mcast_counts;
+    uint32_t  mc_n_groups;
+    void     *mc_members, *mc_groups_d, *mc_out_d, *mc_h;
+    uint64_t  mc_members_cap, mc_groups_d_cap, mc_out_d_cap, mc_h_cap;
     /* poller thread (udpdk_port_attach) */
     pthread_t poller;
     atomic_int poller_run;
@@ -359,6 +376,14 @@ int  h_icmp_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const u
 void h_arp_reset(void);                   /* under tx_lock */
 void h_arp_buffers_free(void);
 int  h_arp_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const uint32_t *meta_dev, uint64_t not_ipv4);
+
+/* mcast.c */
+void h_mcast_reset(void);                 /* under tx_lock */
+void h_mcast_buffers_free(void);
+int  h_mcast_sockopt(int s, int optname, const void *optval, socklen_t optlen);
+void h_mcast_close_locked(int s);         /* under g_udpdk.lock */
+int  h_mcast_apply(void);                 /* under g_udpdk.lock, after h_snapshot_refresh */
+int  h_igmp_stage(udpdk_gpu_ctx *g, int pipe, const udpdk_rx_batch_t *b, const uint32_t *meta_dev, uint64_t not_udp);
 
 /* neigh.c */
 #define H_NEIGH_ENTRIES_DEFAULT 1024u

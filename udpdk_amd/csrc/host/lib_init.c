@@ -46,6 +46,7 @@ static void h_config_defaults(void)
     g_udpdk.icmp_burst = H_ICMP_BURST_DEFAULT;
     g_udpdk.icmp_errors = 0;           /* received ICMP errors are forgotten, as in the reference */
     g_udpdk.arp_on = 0;                /* ARP requests are not answered, as in the reference */
+    g_udpdk.mcast_on = 0;              /* no membership filter and no IGMP, as in the reference */
     g_udpdk.arp_announce = 0;
     g_udpdk.neigh_mode = UDPDK_NEIGH_MODE_OFF;   /* every frame to the [port0_dst] MAC, as in the reference */
     g_udpdk.neigh_entries = H_NEIGH_ENTRIES_DEFAULT;
@@ -82,6 +83,7 @@ void udpdk_host_reset(void)
     h_icmp_reset();
     h_icmp_err_reset();
     h_arp_reset();
+    h_mcast_reset();
     h_neigh_reset();
     pthread_mutex_unlock(&g_udpdk.tx_lock);
     atomic_store(&g_udpdk.interrupted, 0);
@@ -94,6 +96,7 @@ void udpdk_host_reset(void)
     g_udpdk.icmp_burst = H_ICMP_BURST_DEFAULT;
     g_udpdk.icmp_errors = 0;
     g_udpdk.arp_on = 0;
+    g_udpdk.mcast_on = 0;
     g_udpdk.neigh_mode = UDPDK_NEIGH_MODE_OFF;
     pthread_mutex_unlock(&g_udpdk.lock);
 }
@@ -354,6 +357,12 @@ static int h_load_ini(const char *path)
              * 0 (default); checked against [gpu] devices once the file is read */
             if (!strcmp(v, "0") || !strcmp(v, "1")) g_udpdk.arp_on = (uint32_t)(v[0] - '0');
             else { rc = -1; break; }
+        } else if (!strcmp(section, "gpu") && !strcmp(k, "mcast")) {
+            /* 1: a poll filters multicast by the sockets' memberships and answers IGMP queries on the
+             * GPU (udpdk_gpu_rx_mcast, udpdk_gpu_igmp_reply); 0 (default); checked against [gpu]
+             * devices once the file is read */
+            if (!strcmp(v, "0") || !strcmp(v, "1")) g_udpdk.mcast_on = (uint32_t)(v[0] - '0');
+            else { rc = -1; break; }
         } else if (!strcmp(section, "gpu") && !strcmp(k, "arp_announce")) {
             /* 1: udpdk_init queues one RFC 5227 announcement of our address (udpdk_arp_announce) */
             if (!strcmp(v, "0") || !strcmp(v, "1")) g_udpdk.arp_announce = (uint32_t)(v[0] - '0');
@@ -394,6 +403,8 @@ static int h_load_ini(const char *path)
     if (!rc && g_udpdk.icmp_errors && g_udpdk.n_shards > 1) rc = -2;
     /* ... and do not answer ARP (udpdk_config_arp: ENOTSUP; here EINVAL, as for [gpu] icmp) */
     if (!rc && g_udpdk.arp_on && g_udpdk.n_shards > 1) rc = -1;
+    /* ... and neither filter multicast nor answer IGMP (udpdk_config_mcast: ENOTSUP; here EINVAL) */
+    if (!rc && g_udpdk.mcast_on && g_udpdk.n_shards > 1) rc = -1;
     /* ... and learn no neighbours (udpdk_config_neigh: ENOTSUP; here EINVAL, as for [gpu] arp) */
     if (!rc && g_udpdk.neigh_mode && g_udpdk.n_shards > 1) rc = -1;
     return rc;
@@ -512,6 +523,7 @@ void udpdk_cleanup(void)
     h_icmp_buffers_free();
     h_icmp_err_buffers_free();
     h_arp_buffers_free();
+    h_mcast_buffers_free();
     h_neigh_buffers_free();
     h_arenas_free_all();
     g_udpdk.frag_ready = 0;

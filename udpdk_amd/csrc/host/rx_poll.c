@@ -229,12 +229,12 @@ int h_rx_drop_apply(void)
     return 0;
 }
 
-/* What the drop filter, the reuse-port balance and the peer filter removed from one RX result of
- * context g: its counters are classify's (every delivery made) and its deliveries the kept count.
- * (The polls size lane_cap for every delivery, so no input is truncated and the difference is the
- * stages' `removed`.) With one stage on the difference is that stage's; with several, each counter
- * takes its own stage's count, so udpdk_rx_dropped never counts balanced clones or refused
- * datagrams. */
+/* What the drop filter, the reuse-port balance, the peer filter and the membership filter removed
+ * from one RX result of context g: its counters are classify's (every delivery made) and its
+ * deliveries the kept count. (The polls size lane_cap for every delivery, so no input is
+ * truncated and the difference is the stages' `removed`.) With one stage on the difference is
+ * that stage's; with several, each counter takes its own stage's count, so udpdk_rx_dropped
+ * never counts balanced clones, refused datagrams or multicast nobody joined. */
 void h_rx_drop_count(udpdk_gpu_ctx *g, const udpdk_rx_stats_t *st)
 {
     if (st->counters[UDPDK_C_DELIVERIES] <= st->deliveries) return;
@@ -242,14 +242,18 @@ void h_rx_drop_count(udpdk_gpu_ctx *g, const udpdk_rx_stats_t *st)
     const int drop = g_udpdk.rx_drop_applied != 0;
     const int bal = g_udpdk.reuseport_applied == UDPDK_REUSEPORT_BALANCE;
     const int peer = g_udpdk.peer_applied != 0;
-    if (drop + bal + peer == 1) {
-        __atomic_fetch_add(drop ? &g_udpdk.rx_dropped : bal ? &g_udpdk.rx_balanced : &g_udpdk.rx_refused, gone,
-                           __ATOMIC_RELAXED);
-    } else if (drop + bal + peer > 1) {
+    const int mc = g_udpdk.mcast_applied != 0 && g == g_udpdk.gpu;   /* (the main context alone holds it) */
+    if (drop + bal + peer + mc == 1) {
+        __atomic_fetch_add(drop ? &g_udpdk.rx_dropped : bal ? &g_udpdk.rx_balanced : peer ? &g_udpdk.rx_refused :
+                           &g_udpdk.rx_not_member, gone, __ATOMIC_RELAXED);
+    } else if (drop + bal + peer + mc > 1) {
         /* several stages ran: each count from its own stage's result (st is the block context g
          * wrote the call's results to) */
-        uint32_t d = 0, b = 0, r = 0;
-        if (udpdk_gpu_rx_removed(g, st, &d, &b) || udpdk_gpu_rx_peer_removed(g, st, &r)) return;
+        uint32_t d = 0, b = 0, r = 0, m = 0;
+        if (udpdk_gpu_rx_removed(g, st, &d, &b) || udpdk_gpu_rx_peer_removed(g, st, &r) ||
+            udpdk_gpu_rx_mcast_removed(g, st, &m))
+            return;
+        __atomic_fetch_add(&g_udpdk.rx_not_member, m, __ATOMIC_RELAXED);
         __atomic_fetch_add(&g_udpdk.rx_dropped, d, __ATOMIC_RELAXED);
         __atomic_fetch_add(&g_udpdk.rx_balanced, b, __ATOMIC_RELAXED);
         __atomic_fetch_add(&g_udpdk.rx_refused, r, __ATOMIC_RELAXED);
@@ -1244,6 +1248,11 @@ static int h_poll_chunked(const uint8_t *frames, uint64_t frames_bytes, const ui
             err = errno;
             break;
         }
+        /* [gpu] mcast: the chunk's IGMP reports, on its pipe, queued ahead of its ICMP answers */
+        if (h_igmp_stage(g, h_pipe_of(k), &staged, meta_dev, C->st.counters[UDPDK_C_VERDICT0 + UDPDK_V_NOT_UDP])) {
+            err = errno;
+            break;
+        }
         /* [gpu] icmp: the chunk's answers, on its pipe, before reassembly touches the frames */
         if (h_icmp_stage(g, h_pipe_of(k), &staged, meta_dev, &icmp_budget)) { err = errno; break; }
         /* [gpu] icmp_errors: the chunk's ICMP errors for connected sockets, on its pipe */
@@ -1341,7 +1350,7 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
     struct h_arena *ad = NULL, *af = NULL;
     PROF_T(p0);
     if (h_snapshot_refresh()) goto out;
-    if (h_rx_drop_apply() || h_reuseport_apply() || h_peer_apply()) goto out;
+    if (h_rx_drop_apply() || h_reuseport_apply() || h_peer_apply() || h_mcast_apply()) goto out;
     PROF_T(p1);
     const uint32_t lanes = g_udpdk.snap_lanes, maxfan = g_udpdk.snap_maxfan;
     if (g_udpdk.n_shards <= 1) {
@@ -1388,6 +1397,9 @@ int udpdk_poll_rx(const uint8_t *frames, uint64_t frames_bytes, const uint32_t *
         if (h_arp_stage(g, 0, &staged, meta_dev, st.counters[UDPDK_C_VERDICT0 + UDPDK_V_NOT_IPV4])) goto out;
         /* [gpu] neigh: what the batch's ARP teaches the neighbour table, under the same gate */
         if (h_neigh_stage(g, 0, &staged, meta_dev, st.counters[UDPDK_C_VERDICT0 + UDPDK_V_NOT_IPV4])) goto out;
+        /* [gpu] mcast: IGMP reports in answer to the staged batch's queries, under the gate of a frame
+         * that is IPv4 and not UDP (nothing is enqueued with the switch off or no group joined) */
+        if (h_igmp_stage(g, 0, &staged, meta_dev, st.counters[UDPDK_C_VERDICT0 + UDPDK_V_NOT_UDP])) goto out;
         /* [gpu] icmp: echo replies and port-unreachable errors for the staged batch, queued for
          * udpdk_tx_drain, before reassembly touches the frames (nothing is enqueued with flags 0) */
         uint32_t icmp_budget = h_icmp_budget();

@@ -284,6 +284,7 @@ void h_sockets_reset(void)
     __atomic_store_n(&g_udpdk.rx_dropped, 0, __ATOMIC_RELAXED);
     __atomic_store_n(&g_udpdk.rx_balanced, 0, __ATOMIC_RELAXED);
     __atomic_store_n(&g_udpdk.rx_refused, 0, __ATOMIC_RELAXED);
+    g_udpdk.mcast_version++;                   /* (the slots' groups went with the memset too) */
     g_udpdk.n_connected = 0;                   /* (the slots' peers went with the memset) */
     g_udpdk.peer_version++;
     g_udpdk.version++;
@@ -309,6 +310,7 @@ int udpdk_socket(int domain, int type, int protocol)
             sl->ip = 0;
             sl->udp_port = 0;
             sl->connected = 0;
+            sl->n_mc = 0;
             atomic_store(&sl->so_error, 0);
             sl->prev = sl->next = -1;
             g_udpdk.n_active++;
@@ -348,6 +350,8 @@ int udpdk_getsockopt(int s, int level, int optname, void *optval, socklen_t *opt
 
 int udpdk_setsockopt(int s, int level, int optname, const void *optval, socklen_t optlen)
 {
+    /* IP_ADD_MEMBERSHIP / IP_DROP_MEMBERSHIP (mcast.c); any other IPPROTO_IP option: ENOPROTOOPT */
+    if (level == IPPROTO_IP && h_valid_fd(s) && g_udpdk.slots[s].used) return h_mcast_sockopt(s, optname, optval, optlen);
     if (h_sockopt_check(s, level, optname, optval, &optlen)) return -1;
     struct h_slot *sl = &g_udpdk.slots[s];
     const int was = sl->so_options & optname;
@@ -405,6 +409,7 @@ int udpdk_close(int s)
     sl->tx.head = sl->tx.tail = 0;
     pthread_mutex_unlock(&g_udpdk.tx_lock);
     atomic_store(&sl->so_error, 0);
+    h_mcast_close_locked(s);                   /* the groups go with the socket (the last holder's: a leave) */
     if (sl->connected) {                       /* the peer goes with the socket */
         sl->connected = 0;
         g_udpdk.n_connected--;

@@ -22,9 +22,11 @@
 #include "rx_filter.h"
 #include "rx_balance.h"
 #include "rx_peer.h"
+#include "rx_mcast.h"
 #include "icmp_reply.h"
 #include "icmp_error.h"
 #include "arp_reply.h"
+#include "igmp_reply.h"
 #include "neigh.h"
 #include "rss_host.h"
 
@@ -123,7 +125,8 @@ struct ResultSlot {
     void release() { release_all(dev, host); }
 };
 
-// Workspace of a lane-removal stage (lane_stage: the drop filter, the balance, the peer filter),
+// Workspace of a lane-removal stage (lane_stage: the drop filter, the balance, the peer filter, the
+// membership filter),
 // lazily sized: per stage one per pipe for the sticky mode and one for the explicit calls.
 struct FilterWs {
     DevBuf<unsigned long long> mask;
@@ -181,6 +184,16 @@ struct ArpWs {
     void release() { release_all(cand, row, fuse, res); }
 };
 
+// Workspace of the IGMP query responder (igmp_reply.hip), lazily sized by the context's max_frames: one
+// for the context stream (udpdk_gpu_igmp_reply) and one per pipe (udpdk_gpu_pipe_igmp_reply).
+struct IgmpQWs {
+    DevBuf<uint32_t> row;                      // the rows
+    DevBuf<uint32_t> bits;                     // the answer set, zeroed once: every launch leaves zeros
+    DevBuf<unsigned long long> fuse;           // fan-in words, zeroed once: every launch leaves zeros
+    ResultSlot<IgmpQResult> res;
+    void release() { release_all(row, bits, fuse, res); }
+};
+
 // Workspaces of the neighbour stages (neigh.hip), lazily sized: the learn stage has one for the
 // context stream (udpdk_gpu_neigh_learn) and one per pipe (udpdk_gpu_pipe_neigh_learn), the resolve
 // stage one (the context stream).
@@ -196,7 +209,7 @@ using NeighLearnWs = NeighWs<uint4, NeighLearnResult>;
 using NeighResolveWs = NeighWs<uint2, NeighResolveResult>;
 
 // The sticky lane-removal stages, in the order rx_on_pipe applies them.
-enum { ST_DROP, ST_BALANCE, ST_PEER, N_STICKY };
+enum { ST_DROP, ST_BALANCE, ST_PEER, ST_MCAST, N_STICKY };
 
 // One RX pipe = a stream and the per-call workspace. With pipelining depth d > 1, consecutive
 // udpdk_gpu_rx calls rotate over d pipes, so one batch's prologue, tail and compaction overlap
@@ -222,11 +235,12 @@ struct Pipe {
     FilterWs flt;                             // sticky drop filter
     BalanceWs bal;                            // sticky reuse-port balance
     FilterWs peer;                            // sticky peer filter
-    FilterWs *const sticky[N_STICKY] = {&flt, &bal, &peer};
+    FilterWs mcast;                           // sticky membership filter
+    FilterWs *const sticky[N_STICKY] = {&flt, &bal, &peer, &mcast};
     bool sticky_ran[N_STICKY] = {};           // this pipe's last call ran the stage
     const udpdk_rx_stats_t *stats_of = nullptr;   // the stats block read_result filled last, and what each
     uint32_t removed[N_STICKY] = {};              // stage removed in that call (udpdk_gpu_rx_removed,
-                                                  // udpdk_gpu_rx_peer_removed)
+                                                  // udpdk_gpu_rx_peer_removed, udpdk_gpu_rx_mcast_removed)
     // host-resident batches (udpdk_gpu_rx_host[_async]): staging, lazily sized
     DevBuf<uint8_t> st_frames_d, st_desc_d, st_out_d;
     PinnedBuf<uint8_t> st_frames_h, st_desc_h;
@@ -236,11 +250,12 @@ struct Pipe {
     IcmpWs icmp;                              // udpdk_gpu_pipe_icmp_reply on this pipe's stream
     IcmpErrWs icmp_err;                       // udpdk_gpu_pipe_icmp_errors on this pipe's stream
     ArpWs arp;                                // udpdk_gpu_pipe_arp_reply on this pipe's stream
+    IgmpQWs igmp;                             // udpdk_gpu_pipe_igmp_reply on this pipe's stream
     NeighLearnWs nlearn;                      // udpdk_gpu_pipe_neigh_learn on this pipe's stream
     void release()
     {
-        release_all(hist, partial, base, agg, ticket, fuse, tile_cnt, res, flt, bal, peer, st_frames_d,
-                    st_desc_d, st_out_d, st_frames_h, st_desc_h, icmp, icmp_err, arp, nlearn);
+        release_all(hist, partial, base, agg, ticket, fuse, tile_cnt, res, flt, bal, peer, mcast, st_frames_d,
+                    st_desc_d, st_out_d, st_frames_h, st_desc_h, icmp, icmp_err, arp, igmp, nlearn);
     }
 };
 constexpr int MAX_PIPES = 4;
@@ -300,10 +315,17 @@ struct udpdk_gpu_ctx {
     DevBuf<uint2> peer_tab;                   // [max_lanes] its records (off past what was given)
     FilterWs xpeer;                           // explicit udpdk_gpu_rx_peer_select calls
     FilterWs *peer_last = nullptr;            // the last peer filter run (udpdk_gpu_rx_peer_stats)
+    bool mcast_on = false;                    // udpdk_gpu_rx_mcast: the sticky membership filter
+    DevBuf<uint8_t> mcast_mc;                 // [max_lanes] its lane flags (zero past what was given)
+    DevBuf<uint2> mcast_tab;                  // its membership table, 1 << mcast_lg slots
+    uint32_t mcast_lg = 0;
+    FilterWs xmcast;                          // explicit udpdk_gpu_rx_mcast_select calls
+    FilterWs *mcast_last = nullptr;           // the last membership filter run (udpdk_gpu_rx_mcast_stats)
     ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
     IcmpWs icmp;                              // udpdk_gpu_icmp_reply (the context stream)
     IcmpErrWs icmp_err;                       // udpdk_gpu_icmp_errors (the context stream)
     ArpWs arp;                                // udpdk_gpu_arp_reply (the context stream)
+    IgmpQWs igmp;                             // udpdk_gpu_igmp_reply (the context stream)
     DevBuf<uint32_t> neigh_tab;               // udpdk_gpu_neigh_create: four dwords per entry
     uint32_t neigh_entries = 0;               // 0: no table
     NeighLearnWs nlearn;                      // udpdk_gpu_neigh_learn (the context stream)
@@ -334,8 +356,9 @@ struct udpdk_gpu_ctx {
     void release()
     {
         for (Pipe &P : pipes) P.release();
-        release_all(port_tab, binds, slots, hint, xflt, bal_rp, bal_ktab, xbal, peer_tab, xpeer, rpl, icmp,
-                    icmp_err, arp, neigh_tab, nlearn, nresolve, rss_reta, rss_ktab, rss_qid, rss_hist, rss_partial, rss_total, rss_fuse);
+        release_all(port_tab, binds, slots, hint, xflt, bal_rp, bal_ktab, xbal, peer_tab, xpeer, mcast_mc, mcast_tab,
+                    xmcast, rpl, icmp,
+                    icmp_err, arp, igmp, neigh_tab, nlearn, nresolve, rss_reta, rss_ktab, rss_qid, rss_hist, rss_partial, rss_total, rss_fuse);
     }
 };
 
@@ -953,27 +976,50 @@ int peer_enqueue(udpdk_gpu_ctx *c, FilterWs &W, hipStream_t st, const udpdk_rx_b
     return rc;
 }
 
+// The membership filter (rx_mcast.hip): a checked lane's multicast entries of groups it did not join out.
+int mcast_enqueue(udpdk_gpu_ctx *c, FilterWs &W, hipStream_t st, const udpdk_rx_batch_t *bt,
+                  const udpdk_rx_lanes_t *in, const uint8_t *lane_mc, const uint2 *table, uint32_t slots_lg,
+                  uint32_t *off_out, uint32_t *pkt_out, uint32_t out_cap)
+{
+    const int rc = lane_stage(c, W, st, in, off_out, pkt_out, out_cap, [&](FilterArgs &fa) {
+        fa.meta = nullptr;
+        McastMarkArgs ma;
+        ma.f = fa;
+        ma.lane_mc = lane_mc;
+        ma.table = table;
+        ma.frames = bt->frames_dev;
+        ma.offset = bt->offset_dev;
+        ma.length = bt->length_dev;
+        ma.slots_lg = slots_lg;
+        ma.frames_bytes = (uint32_t)bt->frames_bytes;
+        ma.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+        return launch_mark(c, st, rx_mcast_mark, ma, fa);
+    });
+    if (!rc) c->mcast_last = &W;
+    return rc;
+}
+
 int rx_lanes_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udpdk_rx_out_t *o);
 
 // One batch's RX on a pipe: the launch sequence that makes the lanes (whichever form it takes),
 // then the sticky stages that are on (sticky_stage), each on what the one before left, all on the
 // pipe's stream. They are per-entry predicates that do not depend on what else the lanes hold, so
 // they commute: one removes every entry of a frame, one picks by a hash that does not depend on
-// the lanes, one looks at the entry's own lane and frame.
+// the lanes, two look at the entry's own lane and frame.
 int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udpdk_rx_out_t *o)
 {
     int rc = rx_lanes_on_pipe(c, pipe, bt, o);
     if (rc) return rc;
     Pipe &P = c->pipes[pipe];
     for (bool &ran : P.sticky_ran) ran = false;
-    if ((!c->drop_flags && !c->bal_on && !c->peer_on) || bt->n == 0) return 0;   // (no frames: the lanes are empty)
+    if ((!c->drop_flags && !c->bal_on && !c->peer_on && !c->mcast_on) || bt->n == 0) return 0;   // (no frames: the lanes are empty)
     const udpdk_rx_lanes_t in = {o->meta_dev, bt->n, o->lane_off_dev, o->lane_pkt_dev, o->lane_cap, c->n_lanes};
     if (c->drop_flags &&
         (rc = sticky_stage(c, P, ST_DROP, o, [&](uint32_t *off, uint32_t *pkt) {
              return filter_enqueue(c, P.flt, P.stream, &in, c->drop_flags, off, pkt, o->lane_cap);
          })))
         return rc;
-    if (!c->bal_on && !c->peer_on) return 0;
+    if (!c->bal_on && !c->peer_on && !c->mcast_on) return 0;
     if (c->lane_mask != 0xFFFFFFFFu) return -EINVAL;           // compat mode: a lane is not a sockfd
     if (c->bal_on &&
         (rc = sticky_stage(c, P, ST_BALANCE, o, [&](uint32_t *off, uint32_t *pkt) {
@@ -983,6 +1029,12 @@ int rx_on_pipe(udpdk_gpu_ctx *c, int pipe, const udpdk_rx_batch_t *bt, const udp
     if (c->peer_on &&
         (rc = sticky_stage(c, P, ST_PEER, o, [&](uint32_t *off, uint32_t *pkt) {
              return peer_enqueue(c, P.peer, P.stream, bt, &in, c->peer_tab, off, pkt, o->lane_cap);
+         })))
+        return rc;
+    if (c->mcast_on &&
+        (rc = sticky_stage(c, P, ST_MCAST, o, [&](uint32_t *off, uint32_t *pkt) {
+             return mcast_enqueue(c, P.mcast, P.stream, bt, &in, c->mcast_mc, c->mcast_tab, c->mcast_lg, off, pkt,
+                                  o->lane_cap);
          })))
         return rc;
     return 0;
@@ -1356,7 +1408,7 @@ int lanes_check(const udpdk_gpu_ctx *c, const udpdk_rx_lanes_t *in, const uint32
     return 0;
 }
 
-// lanes_check, and what udpdk_gpu_rx_balance_select and udpdk_gpu_rx_peer_select ask besides: the
+// lanes_check, and what udpdk_gpu_rx_balance_select, _peer_select and _mcast_select ask besides: the
 // batch the lanes were made from, lanes that are sockets, outputs apart from the inputs.
 int select_check(const udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_lanes_t *in,
                  const uint32_t *off_out, const uint32_t *pkt_out, uint32_t out_cap)
@@ -1374,7 +1426,7 @@ int select_check(const udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk
 }
 
 // The FilterResult of W's last run into its mirror (and, for the balance stage, the count that goes
-// with it), waited for: what the three *_stats calls read.
+// with it), waited for: what the four *_stats calls read.
 int fetch_filter_result(udpdk_gpu_ctx *c, FilterWs *W, BalanceWs *B = nullptr)
 {
     if (!W) return -ENOENT;
@@ -1540,6 +1592,93 @@ int udpdk_gpu_rx_peer_removed(udpdk_gpu_ctx *c, const udpdk_rx_stats_t *stats, u
     for (const Pipe &P : c->pipes) {
         if (P.stats_of != stats) continue;
         *refused = P.removed[ST_PEER];
+        return 0;
+    }
+    return -ENOENT;
+}
+
+int udpdk_gpu_mcast_table_build(const udpdk_mcast_member_t *members, uint32_t n, udpdk_mcast_member_t *table_out,
+                                uint32_t slots)
+{
+    const uint32_t lg = mcast_slots_log2(slots);
+    if (!table_out || (!members && n) || !lg) return -EINVAL;
+    if (n > slots) return -ENOSPC;
+    udpdk_mcast_member_t *tab = table_out;
+    memset(tab, 0, (size_t)slots * sizeof(*tab));
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t g = members[k].group, l = members[k].lane;
+        if (g == 0u || mcast_probe(tab, lg, g, l)) return -EINVAL;
+        uint32_t i = mcast_start(g, l, lg);
+        while (tab[i].group != 0u) i = (i + 1u) & (slots - 1u);   // (k < slots members are in: a slot is empty)
+        tab[i] = members[k];
+    }
+    return 0;
+}
+
+int udpdk_gpu_rx_mcast_select(udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const udpdk_rx_lanes_t *in,
+                              const uint8_t *lane_mc_dev, const udpdk_mcast_member_t *table_dev, uint32_t slots,
+                              uint32_t *lane_off_out_dev, uint32_t *lane_pkt_out_dev, uint32_t out_cap)
+{
+    const uint32_t lg = mcast_slots_log2(slots);
+    if (!lane_mc_dev || !table_dev || ((uintptr_t)table_dev & 7u) != 0 || !lg) return -EINVAL;   // (8-byte loads)
+    if (select_check(c, bt, in, lane_off_out_dev, lane_pkt_out_dev, out_cap)) return -EINVAL;
+    if (bt->n && !bt->length_dev) return -EINVAL;
+    const int rc = on_ctx_stream(c);
+    if (rc) return rc;
+    return mcast_enqueue(c, c->xmcast, c->stream, bt, in, lane_mc_dev, reinterpret_cast<const uint2 *>(table_dev), lg,
+                         lane_off_out_dev, lane_pkt_out_dev, out_cap);
+}
+
+int udpdk_gpu_rx_mcast(udpdk_gpu_ctx *c, const uint8_t *lane_mc_host, uint32_t n_lanes,
+                       const udpdk_mcast_member_t *members_host, uint32_t n_members)
+{
+    if (!c || n_lanes > c->max_lanes || n_members > (1u << 19) || (!members_host && n_members)) return -EINVAL;
+    HIPC(c, hipSetDevice(c->device));
+    { int rc = sync_all(c); if (rc) return rc; }             // (calls in flight read the flags and the table)
+    if (!lane_mc_host || n_lanes == 0) {
+        c->mcast_on = false;
+        return 0;
+    }
+    for (uint32_t k = 0; k < n_members; ++k)
+        if (members_host[k].lane >= n_lanes) return -EINVAL;
+    uint32_t slots = MCAST_MIN_SLOTS;
+    while (slots < 2u * n_members) slots <<= 1;
+    std::vector<udpdk_mcast_member_t> tab(slots);
+    { int rc = udpdk_gpu_mcast_table_build(members_host, n_members, tab.data(), slots); if (rc) return rc; }
+    std::vector<uint8_t> mc(c->max_lanes, 0);
+    for (uint32_t l = 0; l < n_lanes; ++l) mc[l] = lane_mc_host[l] ? 1 : 0;
+    c->mcast_on = false;                                     // (until both uploads are in)
+    int rc;
+    if ((rc = c->mcast_mc.ensure(c, c->max_lanes)) || (rc = c->mcast_tab.ensure(c, slots))) return rc;
+    HIPC(c, hipMemcpy(c->mcast_mc, mc.data(), mc.size(), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->mcast_tab, tab.data(), (size_t)slots * sizeof(uint2), hipMemcpyHostToDevice));
+    c->mcast_lg = mcast_slots_log2(slots);
+    c->mcast_on = true;
+    return 0;
+}
+
+int udpdk_gpu_rx_mcast_stats(udpdk_gpu_ctx *c, udpdk_rx_mcast_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    const int rc = fetch_filter_result(c, c->mcast_last);
+    if (rc) return rc;
+    const FilterResult *r = c->mcast_last->res.host;
+    st->kept = r->kept;
+    st->removed = r->removed;
+    st->member = (uint32_t)r->dropped[2];
+    st->not_member = (uint32_t)r->dropped[0];
+    st->bad_frame = (uint32_t)r->dropped[1];
+    st->bad_index = r->bad_index;
+    st->truncated = r->truncated;
+    return st->kept > c->mcast_last->out_cap ? -ENOSPC : 0;
+}
+
+int udpdk_gpu_rx_mcast_removed(udpdk_gpu_ctx *c, const udpdk_rx_stats_t *stats, uint32_t *not_member)
+{
+    if (!c || !stats || !not_member) return -EINVAL;
+    for (const Pipe &P : c->pipes) {
+        if (P.stats_of != stats) continue;
+        *not_member = P.removed[ST_MCAST];
         return 0;
     }
     return -ENOENT;
@@ -2468,6 +2607,143 @@ int udpdk_gpu_pipe_arp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_arp_stats_t *st)
     if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
     const ResultSlot<ArpResult> &R = c->pipes[pipe].arp.res;
     return R.ran ? arp_stats_out(R.host, st) : -ENOENT;
+}
+
+namespace {
+
+// Argument checks of udpdk_gpu_igmp_reply and its pipe form: nothing is enqueued unless all pass.
+int igmp_check(const udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
+               const uint32_t *meta_dev, const uint32_t *groups_dev, uint32_t n_groups, const udpdk_igmp_out_t *o)
+{
+    if (!c || !cfg || !bt || !meta_dev || !o) return -EINVAL;
+    if (cfg->src_ip == 0u || n_groups > IGMP_MAX_GROUPS || (!groups_dev && n_groups)) return -EINVAL;
+    if (bt->frames_bytes >= (1ull << 32)) return -EINVAL;
+    if (!o->frames_dev || !o->group_index_dev) return -EINVAL;
+    if ((uintptr_t)o->frames_dev & 15u) return -EINVAL;
+    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
+    if (bt->frames_dev) {
+        // the frame buffer with its tailroom against the slots and the index entries
+        const uintptr_t f0 = (uintptr_t)bt->frames_dev, f1 = f0 + bt->frames_bytes + UDPDK_GPU_FRAMES_TAILROOM;
+        const uintptr_t o0 = (uintptr_t)o->frames_dev, o1 = o0 + (uint64_t)o->max_reports * IGMP_SLOT;
+        const uintptr_t g0 = (uintptr_t)o->group_index_dev, g1 = g0 + (uint64_t)o->max_reports * 4u;
+        if ((o0 < f1 && f0 < o1) || (g0 < f1 && f0 < g1)) return -EINVAL;
+    }
+    return 0;
+}
+
+// The stage (igmp_reply.hip) on stream st with workspace W: one launch.
+int igmp_enqueue(udpdk_gpu_ctx *c, IgmpQWs &W, hipStream_t st, const udpdk_tx_config_t *cfg,
+                 const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, const uint32_t *groups_dev, uint32_t n_groups,
+                 const udpdk_igmp_out_t *o)
+{
+    const uint32_t nb = ceil_div(bt->n, IGMP_TILE);
+    const size_t rows = std::max<size_t>(ceil_div(std::max(bt->n, c->max_frames), IGMP_TILE), 1);
+    int rc;
+    if ((rc = W.row.ensure(c, rows * IGMP_ROW)) || (rc = W.res.ensure(c))) return rc;
+    if (!W.fuse) {
+        if ((rc = W.fuse.ensure(c, FUSE_BYTES / 8))) return rc;
+        HIPC(c, hipMemsetAsync(W.fuse, 0, FUSE_BYTES, st));
+    }
+    if (!W.bits) {                               // (each on its own: one may fail where the other did not)
+        if ((rc = W.bits.ensure(c, IGMP_WORDS))) return rc;
+        HIPC(c, hipMemsetAsync(W.bits, 0, IGMP_WORDS * sizeof(uint32_t), st));
+    }
+    if (!bt->n) {
+        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(IgmpQResult), st));
+        W.res.ran = true;
+        return 0;
+    }
+    IgmpQArgs ga;
+    ga.frames = bt->frames_dev;
+    ga.offset = bt->offset_dev;
+    ga.length = bt->length_dev;
+    ga.meta = meta_dev;
+    ga.groups = groups_dev;
+    ga.out = o->frames_dev;
+    ga.group_index = o->group_index_dev;
+    ga.row = W.row;
+    ga.bits = W.bits;
+    ga.fuse = W.fuse;
+    ga.res = W.res.dev;
+    ga.n = bt->n;
+    ga.n_blocks = nb;
+    ga.frames_bytes = (uint32_t)bt->frames_bytes;
+    ga.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
+    ga.n_groups = n_groups;
+    ga.max_reports = o->max_reports;
+    ga.src_ip = cfg->src_ip;
+    ga.mac_lo = ga.mac_hi = 0u;
+    memcpy(&ga.mac_lo, cfg->src_mac, 4);
+    memcpy(&ga.mac_hi, cfg->src_mac + 4, 2);
+    hipLaunchKernelGGL(igmp_reply, dim3(nb), dim3(IGMP_BLOCK), 0, st, ga);
+    HIPC(c, hipGetLastError());
+    W.res.ran = true;
+    return 0;
+}
+
+int igmp_stats_out(const IgmpQResult *r, udpdk_igmp_stats_t *st)
+{
+    st->igmp = r->c[IGMP_R_IGMP];
+    st->malformed = r->c[IGMP_R_MALFORMED];
+    st->bad_cksum = r->c[IGMP_R_BAD_CKSUM];
+    st->other_type = r->c[IGMP_R_OTHER_TYPE];
+    st->bad_dst = r->c[IGMP_R_BAD_DST];
+    st->general = r->c[IGMP_R_GENERAL];
+    st->not_member = r->c[IGMP_R_NOT_MEMBER];
+    st->specific = r->c[IGMP_R_SPECIFIC];
+    st->reports = r->reports;
+    st->no_room = r->no_room;
+    st->bad_frame = r->c[IGMP_R_BAD_FRAME];
+    return st->no_room ? -ENOSPC : 0;
+}
+
+} // namespace
+
+int udpdk_gpu_igmp_geometry(uint32_t n, uint32_t *frames_per_block, uint32_t *n_blocks)
+{
+    if (!frames_per_block || !n_blocks) return -EINVAL;
+    *frames_per_block = IGMP_TILE;
+    *n_blocks = std::max<uint32_t>(1u, ceil_div(n, IGMP_TILE));
+    return 0;
+}
+
+int udpdk_gpu_igmp_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
+                         const uint32_t *meta_dev, const uint32_t *groups_dev, uint32_t n_groups,
+                         const udpdk_igmp_out_t *o)
+{
+    int rc = igmp_check(c, cfg, bt, meta_dev, groups_dev, n_groups, o);
+    if (rc) return rc;
+    if ((rc = on_ctx_stream(c))) return rc;
+    return igmp_enqueue(c, c->igmp, c->stream, cfg, bt, meta_dev, groups_dev, n_groups, o);
+}
+
+int udpdk_gpu_igmp_stats(udpdk_gpu_ctx *c, udpdk_igmp_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    const int rc = ctx_result(c, c->igmp.res);
+    return rc ? rc : igmp_stats_out(c->igmp.res.host, st);
+}
+
+int udpdk_gpu_pipe_igmp_reply(udpdk_gpu_ctx *c, int pipe, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
+                              const uint32_t *meta_dev, const uint32_t *groups_dev, uint32_t n_groups,
+                              const udpdk_igmp_out_t *o)
+{
+    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    int rc = igmp_check(c, cfg, bt, meta_dev, groups_dev, n_groups, o);
+    if (rc) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    Pipe &P = c->pipes[pipe];
+    P.dirty = true;
+    if ((rc = igmp_enqueue(c, P.igmp, P.stream, cfg, bt, meta_dev, groups_dev, n_groups, o))) return rc;
+    // the counts follow on the pipe's stream: udpdk_gpu_pipe_igmp_stats reads them after udpdk_gpu_pipe_wait
+    return P.igmp.res.enqueue_fetch(c, P.stream);
+}
+
+int udpdk_gpu_pipe_igmp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_igmp_stats_t *st)
+{
+    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
+    const ResultSlot<IgmpQResult> &R = c->pipes[pipe].igmp.res;
+    return R.ran ? igmp_stats_out(R.host, st) : -ENOENT;
 }
 
 namespace {
