@@ -10,7 +10,7 @@ LIB       := udpdk_amd/libudpdk_amd.so
 OBJDIR    := build/obj
 
 HIP_SRC   := udpdk_amd/csrc/rx_classify.hip udpdk_amd/csrc/rx_lanes.hip udpdk_amd/csrc/rx_gather.hip udpdk_amd/csrc/rx_reasm.hip \
-             udpdk_amd/csrc/rx_rss.hip udpdk_amd/csrc/tx_kernels.hip udpdk_amd/csrc/tx_reply.hip udpdk_amd/csrc/rx_filter.hip udpdk_amd/csrc/rx_balance.hip udpdk_amd/csrc/rx_peer.hip udpdk_amd/csrc/rx_mcast.hip udpdk_amd/csrc/icmp_reply.hip udpdk_amd/csrc/icmp_error.hip udpdk_amd/csrc/arp_reply.hip udpdk_amd/csrc/igmp_reply.hip udpdk_amd/csrc/neigh.hip \
+             udpdk_amd/csrc/rx_rss.hip udpdk_amd/csrc/tx_kernels.hip udpdk_amd/csrc/tx_reply.hip udpdk_amd/csrc/tx_segment.hip udpdk_amd/csrc/rx_filter.hip udpdk_amd/csrc/rx_balance.hip udpdk_amd/csrc/rx_peer.hip udpdk_amd/csrc/rx_mcast.hip udpdk_amd/csrc/icmp_reply.hip udpdk_amd/csrc/icmp_error.hip udpdk_amd/csrc/arp_reply.hip udpdk_amd/csrc/igmp_reply.hip udpdk_amd/csrc/neigh.hip \
              udpdk_amd/csrc/udpdk_gpu.hip
 C_SRC     := $(wildcard udpdk_amd/csrc/host/*.c)
 HIP_OBJ   := $(patsubst udpdk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))

@@ -463,6 +463,49 @@ typedef struct {
 } udpdk_neigh_counts_t;
 int udpdk_neigh_counts(udpdk_neigh_counts_t *counts);
 
+/* Segmented sends: Linux's UDP_SEGMENT. One send carries the payload of up to UDPDK_GSO_MAX_SEGS
+ * (64, Linux's UDP_MAX_SEGMENTS) datagrams plus a segment size g, is queued as one ring entry with
+ * its payload stored once, and udpdk_tx_drain cuts it on the GPU (udpdk_gpu_tx_segment_plan,
+ * udpdk_gpu.h): datagrams of g bytes, the last one the remainder, all to the send's destination.
+ *   - udpdk_setsockopt(s, IPPROTO_UDP (= SOL_UDP), UDP_SEGMENT, &int, len) stores the socket's size,
+ *     0..65535 (0: off); a negative value, one above 65535 or optlen < sizeof(int): EINVAL.
+ *     udpdk_getsockopt returns it. Any other IPPROTO_UDP option keeps the answer it always had
+ *     (EINVAL, as for every level but SOL_SOCKET and IPPROTO_IP). udpdk_close and
+ *     udpdk_host_reset clear it. udpdk_sendto, udpdk_send and udpdk_sendmsg honour it alike.
+ *   - udpdk_sendmsg gathers msg_iov in order into one payload; msg_name is the destination, or NULL
+ *     for the peer of a connected socket, by udpdk_sendto's rules (as are the pending error, the
+ *     auto-bind, ENOBUFS and EMSGSIZE). A control message SOL_UDP / UDP_SEGMENT of
+ *     CMSG_LEN(sizeof(uint16_t)) overrides the socket's size for this call; another length, or any
+ *     other control message: EINVAL. Without a size in force it is udpdk_sendto of the gathered bytes.
+ *   - with a size g > 0 in force (Linux's udp_send_skb): 28 + g > mtu (udpdk_config_mtu) gives
+ *     EINVAL whatever the length, so a segment never fragments; len > g * UDPDK_GSO_MAX_SEGS gives
+ *     EINVAL; len > 65507 gives EMSGSIZE; len <= g is queued as an ordinary datagram; otherwise the
+ *     call queues one entry and returns len.
+ *   - udpdk_tx_drain treats a send as a unit: its frames and bytes count against the drain's limits
+ *     as a whole (udpdk_gpu_tx_segment_span), its segments are consecutive frames and never split
+ *     across drains, a send no drain with these limits can carry is dropped and counted once in
+ *     udpdk_tx_dropped, and udpdk_tx_pending counts a queued send as one. A drain that selected no
+ *     such send launches what it always launched. With the neighbour cache on, every segment is
+ *     resolved, and an unresolved one counts once in tx_unresolved.
+ * One divergence from Linux: there segments are always checksummed and a socket with checksums off
+ * is refused; here they follow udpdk_config_tx_cksum like every other datagram. The IPv4 id stays 0,
+ * as in everything this stack sends. Not done: UDP_GRO, udpdk_poll_echo, MSG_MORE / corking (flags
+ * must be 0), recvmsg. */
+#ifndef SOL_UDP
+#define SOL_UDP 17
+#endif
+#ifndef UDP_SEGMENT
+#define UDP_SEGMENT 103
+#endif
+ssize_t udpdk_sendmsg(int s, const struct msghdr *msg, int flags);
+/* Session sums: sends queued with more than one segment, their segments, the drains that launched
+ * the segment plan, and the sends refused with EINVAL by the size rules above. udpdk_host_reset
+ * zeroes them. */
+typedef struct {
+    uint64_t sends, segments, plans, refused;
+} udpdk_gso_counts_t;
+int udpdk_gso_counts(udpdk_gso_counts_t *counts);
+
 /* Socket slot state (exch_slot_info, udpdk_types.h:40-47) for the GPU TX slot table. */
 int udpdk_slot_table(udpdk_slot_t *slots, uint32_t n_slots);
 

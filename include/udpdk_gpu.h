@@ -63,7 +63,9 @@ extern "C" {
  *    udpdk_gpu_tx_build_neigh were added)
  *    (still 3: udpdk_gpu_rx_mcast_select / udpdk_gpu_rx_mcast / udpdk_gpu_rx_mcast_stats /
  *    udpdk_gpu_rx_mcast_removed / udpdk_gpu_mcast_table_build, udpdk_gpu_igmp_reply / _stats /
- *    _geometry and udpdk_gpu_pipe_igmp_reply / _stats were added) */
+ *    _geometry and udpdk_gpu_pipe_igmp_reply / _stats were added)
+ *    (still 3: udpdk_gpu_tx_segment_plan / udpdk_gpu_tx_segment / udpdk_gpu_tx_segment_stats /
+ *    udpdk_gpu_tx_segment_span / udpdk_gpu_tx_segment_geometry were added) */
 #define UDPDK_GPU_ABI_VERSION 3
 
 /* ---------------------------------------------------------------------------------------------
@@ -868,6 +870,106 @@ int udpdk_gpu_tx_reply_stats(udpdk_gpu_ctx *ctx, udpdk_tx_reply_stats_t *stats);
 /* Entries per workgroup of the plan kernels and the workgroup count for `count` entries (host
  * only, like udpdk_gpu_rx_geometry). */
 int udpdk_gpu_tx_reply_geometry(uint32_t count, uint32_t *entries_per_block, uint32_t *n_blocks);
+
+/* ---------------------------------------------------------------------------------------------
+ * TX segmentation: Linux's UDP_SEGMENT on the device. One send carries the payload of up to
+ * UDPDK_GSO_MAX_SEGS datagrams plus a segment size, and the stack cuts it: a segment plan turns k
+ * sends in device memory into the descriptor arrays of a udpdk_tx_batch_t with one entry per
+ * segment, over the same payload buffer, and tx_build does the rest. No host loop over datagrams.
+ *
+ * Send j of [0, k) has nseg_j segments:
+ *   0                     when it is skipped (below)
+ *   1                     when gso_size == 0 or payload_len <= gso_size; a zero-length send is one
+ *                         empty datagram
+ *   ceil(len / gso_size)  otherwise
+ * A send is skipped, with no descriptors and no output bytes, in this order of precedence:
+ *   skipped    sockfd < 0
+ *   too_long   payload_len > 65507
+ *   bad_range  payload_off + payload_len > payload_bytes (no payload byte is read by the plan in
+ *              any case)
+ *   too_many   seg_limit != 0 && nseg > seg_limit
+ *   no_room    its last segment index would reach max_segs, or its frames would end past out_cap,
+ *              both counted over every send the rules above let through. Both prefixes are
+ *              monotone, so the sends out of room are a tail. A send is all or nothing and is never
+ *              split.
+ * Placement:
+ *   seg_off[j]      exclusive prefix of nseg; N = seg_off[k]
+ *   segment m = seg_off[j] + t gets
+ *   payload_off[m]  payload_off_j + t * gso_size
+ *   payload_len[m]  min(gso_size, len_j - t * gso_size) (len_j for the one segment of a send that
+ *                   is not cut)
+ *   sockfd[m], dst_ip[m], dst_port[m]   send j's
+ *   frame_off[m]    exclusive prefix of udpdk_gpu_tx_span(payload_len[m], mtu) over the segments,
+ *                   summed in 64 bits; frame_off[N] = where the output ends (<= out_cap). Within a
+ *                   send, frame_off = base_j + t * span(gso_size).
+ * A segment may itself exceed the MTU and fragment: the span rule covers it and tx_build does the
+ * rest (the socket layer never produces that case). Descriptor slots m in [N, max_segs) get
+ * sockfd -1 and zeros, and frame_off[m] for m in (N, max_segs] the output's end, so tx_build over
+ * n = max_segs is correct without a host synchronisation: it writes nothing for a negative sockfd.
+ *
+ * Both calls are asynchronous on the context stream and join the pipes as udpdk_gpu_tx_build does.
+ * -EINVAL, with nothing enqueued: a NULL pointer, a bad mtu (udpdk_gpu_tx_build_mtu's rule) or
+ * flags, out_cap or payload_bytes >= 2^32, max_segs == 0, k + max_segs >= 2^32, and for
+ * udpdk_gpu_tx_segment what udpdk_gpu_tx_build_flags refuses (alignment, no slot table). k == 0
+ * returns 0. The plan launches are not event-timed (udpdk_gpu_timing_read).
+ *
+ * Not part of this interface: receive-side coalescing (UDP_GRO), udpdk_poll_echo, MSG_MORE /
+ * corking, recvmsg.
+ * ------------------------------------------------------------------------------------------- */
+#define UDPDK_GSO_MAX_SEGS 64u      /* Linux's UDP_MAX_SEGMENTS: what the socket layer lets one send carry */
+
+typedef struct {                    /* all [k], against one payload buffer */
+    const uint8_t  *payload_dev;     /* tx_build's tailroom contract (udpdk_tx_batch_t)          */
+    uint64_t        payload_bytes;
+    const uint32_t *payload_off_dev;
+    const uint16_t *payload_len_dev;
+    const uint16_t *gso_size_dev;
+    const int32_t  *sockfd_dev;
+    const uint32_t *dst_ip_dev;
+    const uint16_t *dst_port_dev;
+    uint32_t        k;
+} udpdk_tx_sends_t;
+
+typedef struct {                    /* all [max_segs] except frame_off_dev [max_segs + 1], seg_off_dev [k + 1] */
+    uint32_t *payload_off_dev; uint16_t *payload_len_dev; int32_t *sockfd_dev;
+    uint32_t *dst_ip_dev; uint16_t *dst_port_dev; uint32_t *frame_off_dev;
+    uint32_t *seg_off_dev;
+    uint32_t  max_segs;
+} udpdk_tx_segment_plan_t;
+
+int udpdk_gpu_tx_segment_plan(udpdk_gpu_ctx *ctx, const udpdk_tx_sends_t *sends, uint32_t mtu,
+                              uint32_t seg_limit, uint64_t out_cap, const udpdk_tx_segment_plan_t *plan);
+/* The plan, then udpdk_gpu_tx_build_flags over {sends->payload_dev, sends->payload_bytes, the plan's
+ * arrays, n = max_segs} into {frames_out_dev, out_cap, plan->frame_off_dev}: mtu and flags as there
+ * (that launch is timed as always). */
+int udpdk_gpu_tx_segment(udpdk_gpu_ctx *ctx, const udpdk_tx_config_t *cfg, const udpdk_tx_sends_t *sends,
+                         uint32_t mtu, uint32_t flags, uint32_t seg_limit, uint8_t *frames_out_dev,
+                         uint64_t out_cap, const udpdk_tx_segment_plan_t *plan);
+
+typedef struct {
+    uint64_t bytes_needed;   /* the out_cap with which no send is out of room                    */
+    uint64_t segs_needed;    /* the max_segs with which no send is out of room                   */
+    uint32_t sends;          /* sends that produced segments                                     */
+    uint32_t segments;       /* N                                                                */
+    uint32_t frames;         /* output frames of those segments, fragments included              */
+    uint32_t skipped;        /* sockfd < 0                                                       */
+    uint32_t too_long;
+    uint32_t bad_range;
+    uint32_t too_many;
+    uint32_t no_room;
+} udpdk_tx_segment_stats_t;
+/* Of the last plan on the context (-ENOENT when there was none). Synchronises. -ENOSPC when
+ * no_room > 0. */
+int udpdk_gpu_tx_segment_stats(udpdk_gpu_ctx *ctx, udpdk_tx_segment_stats_t *stats);
+/* Output bytes of one send of `len` payload bytes cut at `gso` and its segment and frame counts, by
+ * the definition above without the skip rules (host helper, needs no GPU): with q = len / gso and
+ * r = len % gso, q * span(gso) + (r ? span(r) : 0); span(len) and one segment when gso == 0 or
+ * len <= gso. nseg and n_frames may be NULL. */
+uint64_t udpdk_gpu_tx_segment_span(uint32_t len, uint32_t gso, uint32_t mtu, uint32_t *nseg, uint32_t *n_frames);
+/* Sends and segments per workgroup of the plan kernels and the workgroup counts for k sends and
+ * max_segs segments (host only, like udpdk_gpu_tx_reply_geometry). */
+int udpdk_gpu_tx_segment_geometry(uint32_t k, uint32_t max_segs, uint32_t *sends_per_block,
+                                  uint32_t *segs_per_block, uint32_t *send_blocks, uint32_t *seg_blocks);
 
 /* ---------------------------------------------------------------------------------------------
  * ICMP on the device: echo replies and port-unreachable errors. The reference has no ICMP: an echo

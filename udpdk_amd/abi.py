@@ -197,6 +197,49 @@ class TxReplyStats(C.Structure):
                 ("frames", C.c_uint32)]
 
 
+GSO_MAX_SEGS = 64         # UDPDK_GSO_MAX_SEGS
+SOL_UDP, UDP_SEGMENT = 17, 103
+
+
+class TxSends(C.Structure):
+    """udpdk_tx_sends_t: the arrays are [k]."""
+    _fields_ = [("payload_dev", C.c_void_p), ("payload_bytes", C.c_uint64), ("payload_off_dev", C.c_void_p),
+                ("payload_len_dev", C.c_void_p), ("gso_size_dev", C.c_void_p), ("sockfd_dev", C.c_void_p),
+                ("dst_ip_dev", C.c_void_p), ("dst_port_dev", C.c_void_p), ("k", C.c_uint32)]
+
+
+class TxSegmentPlan(C.Structure):
+    """udpdk_tx_segment_plan_t: all [max_segs] except frame_off_dev [max_segs + 1], seg_off_dev [k + 1]."""
+    _fields_ = [("payload_off_dev", C.c_void_p), ("payload_len_dev", C.c_void_p), ("sockfd_dev", C.c_void_p),
+                ("dst_ip_dev", C.c_void_p), ("dst_port_dev", C.c_void_p), ("frame_off_dev", C.c_void_p),
+                ("seg_off_dev", C.c_void_p), ("max_segs", C.c_uint32)]
+
+
+SEGMENT_STATS = ("bytes_needed", "segs_needed", "sends", "segments", "frames", "skipped", "too_long", "bad_range",
+                 "too_many", "no_room")
+
+
+class TxSegmentStats(C.Structure):
+    """udpdk_tx_segment_stats_t"""
+    _fields_ = [(k, C.c_uint64 if k.endswith("_needed") else C.c_uint32) for k in SEGMENT_STATS]
+
+
+class GsoCounts(C.Structure):
+    """udpdk_gso_counts_t (udpdk_api.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("sends", "segments", "plans", "refused")]
+
+
+class IoVec(C.Structure):
+    _fields_ = [("iov_base", C.c_void_p), ("iov_len", C.c_size_t)]
+
+
+class MsgHdr(C.Structure):
+    """struct msghdr (Linux, 64-bit)"""
+    _fields_ = [("msg_name", C.c_void_p), ("msg_namelen", C.c_uint32), ("msg_iov", C.POINTER(IoVec)),
+                ("msg_iovlen", C.c_size_t), ("msg_control", C.c_void_p), ("msg_controllen", C.c_size_t),
+                ("msg_flags", C.c_int)]
+
+
 ICMP_ECHO, ICMP_UNREACH, ICMP_ALL, ICMP_UNREACH_BYTES = 1, 2, 3, 70
 
 
@@ -408,6 +451,14 @@ _PROTOS = {
                                      C.POINTER(TxReplyPlan)]),
     "udpdk_gpu_tx_reply_stats": (C.c_int, [_P, C.POINTER(TxReplyStats)]),
     "udpdk_gpu_tx_reply_geometry": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_tx_segment_plan": (C.c_int, [_P, C.POINTER(TxSends), C.c_uint32, C.c_uint32, C.c_uint64,
+                                            C.POINTER(TxSegmentPlan)]),
+    "udpdk_gpu_tx_segment": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(TxSends), C.c_uint32, C.c_uint32, C.c_uint32,
+                                       _P, C.c_uint64, C.POINTER(TxSegmentPlan)]),
+    "udpdk_gpu_tx_segment_stats": (C.c_int, [_P, C.POINTER(TxSegmentStats)]),
+    "udpdk_gpu_tx_segment_span": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint32)]),
+    "udpdk_gpu_tx_segment_geometry": (C.c_int, [C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4),
     "udpdk_gpu_icmp_reply": (C.c_int, [_P, C.POINTER(TxConfig), C.POINTER(RxBatch), _P, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.POINTER(IcmpOut)]),
     "udpdk_gpu_icmp_stats": (C.c_int, [_P, C.POINTER(IcmpStats)]),
@@ -503,6 +554,8 @@ _PROTOS = {
     "udpdk_neigh_add": (C.c_int, [C.c_uint32, _P]),
     "udpdk_neigh_flush": (C.c_int, []),
     "udpdk_neigh_counts": (C.c_int, [C.POINTER(NeighCounts)]),
+    "udpdk_sendmsg": (C.c_ssize_t, [C.c_int, C.POINTER(MsgHdr), C.c_int]),
+    "udpdk_gso_counts": (C.c_int, [C.POINTER(GsoCounts)]),
     "udpdk_sock_error_post": (C.c_int, [C.c_int, C.c_uint32, C.c_uint16, C.c_uint32]),
     "udpdk_icmp_err_counts": (C.c_int, [C.POINTER(IcmpErrCounts)]),
     "udpdk_sock_rx_inject": (C.c_int, [C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint16]),
@@ -1114,6 +1167,88 @@ def tx_reply_run(ctx: GpuContext, cfg: TxConfig, b: RxDeviceBatch, lane_off, lan
                      out_ptr=out_ptr)
 
 
+def tx_segment_span(length: int, gso: int, mtu: int) -> tuple[int, int, int]:
+    """udpdk_gpu_tx_segment_span: (output bytes, segments, frames) of one send (host only)."""
+    ns, nf = C.c_uint32(), C.c_uint32()
+    span = lib().udpdk_gpu_tx_segment_span(length, gso, mtu, C.byref(ns), C.byref(nf))
+    return int(span), ns.value, nf.value
+
+
+def tx_segment_geometry(k: int, max_segs: int) -> tuple[int, int, int, int]:
+    """(sends per workgroup, segments per workgroup, send workgroups, segment workgroups) of the
+    segment plan kernels."""
+    v = [C.c_uint32() for _ in range(4)]
+    _check(lib().udpdk_gpu_tx_segment_geometry(k, max_segs, *[C.byref(x) for x in v]), "udpdk_gpu_tx_segment_geometry")
+    return tuple(x.value for x in v)
+
+
+def tx_segment_stats(ctx: GpuContext) -> tuple[int, TxSegmentStats]:
+    st = TxSegmentStats()
+    rc = lib().udpdk_gpu_tx_segment_stats(ctx.handle, C.byref(st))
+    return rc, st
+
+
+SEND_FIELDS = (("payload_off", np.uint32), ("payload_len", np.uint16), ("gso_size", np.uint16), ("sockfd", np.int32),
+               ("dst_ip", np.uint32), ("dst_port", np.uint16))
+
+
+def _tx_segment(ctx: GpuContext, cfg, payload: np.ndarray, payload_bytes: int, sends: dict, max_segs: int, *, mtu: int,
+                flags: int, seg_limit: int, out_cap: int, k, pad: int, guard: int, null=None):
+    ka = len(sends["payload_off"])                    # what is allocated; k: what the call is told
+    k = ka if k is None else k
+    bufs = [ctx.upload(np.ascontiguousarray(payload, np.uint8))]
+    ins = [ctx.upload(np.ascontiguousarray(sends[name], dt) if len(sends[name]) else np.zeros(1, dt))
+           for name, dt in SEND_FIELDS]
+    # the plan arrays, `pad` elements longer than the call may write, every byte 0xA5
+    arrs = []
+    for name, dt in PLAN_FIELDS + (("seg_off", np.uint32),):
+        m = (ka + 1 if name == "seg_off" else max_segs + (1 if name == "frame_off" else 0)) + pad
+        arrs.append(ctx.upload(np.full(max(1, m) * np.dtype(dt).itemsize, 0xA5, np.uint8)))
+    out = ctx.upload(np.full(out_cap + guard, 0xEE, np.uint8)) if cfg is not None else None
+    bufs += ins + arrs + ([out] if out is not None else [])
+    try:
+        sd = TxSends(bufs[0].ptr, payload_bytes, *[x.ptr for x in ins], k)
+        plan = TxSegmentPlan(*[a.ptr for a in arrs], max_segs)
+        if null is not None:                          # ("sends" | "plan", field): that pointer is NULL
+            setattr(sd if null[0] == "sends" else plan, null[1], None)
+        if cfg is None:
+            rc = lib().udpdk_gpu_tx_segment_plan(ctx.handle, C.byref(sd), mtu, seg_limit, out_cap, C.byref(plan))
+        else:
+            rc = lib().udpdk_gpu_tx_segment(ctx.handle, C.byref(cfg), C.byref(sd), mtu, flags, seg_limit,
+                                            C.c_void_p(out.ptr), out_cap, C.byref(plan))
+        ctx.sync()
+        res = {"rc": rc}
+        for (name, dt), a in zip(PLAN_FIELDS + (("seg_off", np.uint32),), arrs):
+            m = (ka + 1 if name == "seg_off" else max_segs + (1 if name == "frame_off" else 0)) + pad
+            res[name] = ctx.download(a, dt, m)
+        if out is not None:
+            res["out"] = ctx.download(out, np.uint8, out_cap + guard)
+        return res
+    finally:
+        for x in bufs:
+            x.free()
+
+
+def tx_segment_plan_run(ctx: GpuContext, payload: np.ndarray, payload_bytes: int, sends: dict, max_segs: int, *,
+                        mtu: int = 0, seg_limit: int = 0, out_cap: int = 1 << 24, k=None, pad: int = 8, null=None):
+    """udpdk_gpu_tx_segment_plan over host sends: a dict of the six SEND_FIELDS arrays, against
+    `payload` (uploaded whole, tailroom included; payload_bytes is what the call is told). Returns a
+    dict: rc of the call, the six plan arrays and seg_off as downloaded, each `pad` elements longer
+    than the call may write and pre-filled with 0xA5 bytes. null = ("sends" | "plan", field) passes that
+    pointer as NULL."""
+    return _tx_segment(ctx, None, payload, payload_bytes, sends, max_segs, mtu=mtu, flags=0, seg_limit=seg_limit,
+                       out_cap=out_cap, k=k, pad=pad, guard=0, null=null)
+
+
+def tx_segment_run(ctx: GpuContext, cfg: TxConfig, payload: np.ndarray, payload_bytes: int, sends: dict,
+                   max_segs: int, *, mtu: int = 0, flags: int = 0, seg_limit: int = 0, out_cap: int = 1 << 20, k=None,
+                   pad: int = 8, guard: int = 4096):
+    """udpdk_gpu_tx_segment the same way; res["out"] is the output buffer, out_cap + guard bytes
+    pre-filled with 0xEE. The snapshot with the slot table must have been uploaded."""
+    return _tx_segment(ctx, cfg, payload, payload_bytes, sends, max_segs, mtu=mtu, flags=flags, seg_limit=seg_limit,
+                       out_cap=out_cap, k=k, pad=pad, guard=guard)
+
+
 def icmp_geometry(n: int) -> tuple[int, int]:
     """(frames per workgroup, workgroups) of the ICMP scan and build kernels for n frames."""
     e = C.c_uint32()
@@ -1479,6 +1614,12 @@ def sockaddr_in(ip: str | int, port_host: int) -> bytes:
     return struct.pack("<H", socket.AF_INET) + struct.pack(">H", port_host) + ipb + b"\0" * 8
 
 
+def cmsg(level: int, typ: int, data: bytes) -> bytes:
+    """One control message as CMSG_SPACE bytes (Linux, 64-bit: a 16-byte header, 8-byte alignment)."""
+    ln = 16 + len(data)
+    return (struct.pack("<QII", ln, level, typ) + data).ljust((ln + 7) & ~7, b"\0")
+
+
 def raw_ip(ip: str) -> int:
     """Raw network-order IPv4 as the reference holds it (s_addr read as a LE integer)."""
     return struct.unpack("<I", socket.inet_aton(ip))[0]
@@ -1527,6 +1668,32 @@ class HostApi:
         a = C.create_string_buffer(sockaddr_in(ip, port_host), 16)
         buf = C.create_string_buffer(payload, max(1, len(payload)))
         return self.L.udpdk_sendto(s, buf, len(payload), flags, a, 16)
+
+    def sendmsg(self, s, parts, ip=None, port_host: int = 0, *, gso: int | None = None, control: bytes | None = None,
+                flags: int = 0) -> int:
+        """udpdk_sendmsg: `parts` are the iovecs' bytes in order; ip None passes a NULL msg_name; gso adds
+        a SOL_UDP / UDP_SEGMENT control message (control: raw control bytes instead)."""
+        keep = [C.create_string_buffer(p, max(1, len(p))) for p in parts]
+        iov = (IoVec * max(1, len(parts)))()
+        for i, p in enumerate(parts):
+            iov[i].iov_base = C.cast(keep[i], C.c_void_p)
+            iov[i].iov_len = len(p)
+        m = MsgHdr()
+        if ip is not None:
+            a = C.create_string_buffer(sockaddr_in(ip, port_host), 16)
+            m.msg_name, m.msg_namelen = C.cast(a, C.c_void_p), 16
+        m.msg_iov, m.msg_iovlen = iov, len(parts)
+        if control is None and gso is not None:
+            control = cmsg(SOL_UDP, UDP_SEGMENT, struct.pack("<H", gso))
+        if control:
+            cb = C.create_string_buffer(control, len(control))
+            m.msg_control, m.msg_controllen = C.cast(cb, C.c_void_p), len(control)
+        return self.L.udpdk_sendmsg(s, C.byref(m), flags)
+
+    def gso_counts(self) -> dict[str, int]:
+        c = GsoCounts()
+        _check(self.L.udpdk_gso_counts(C.byref(c)), "udpdk_gso_counts")
+        return {k: int(getattr(c, k)) for k, _ in GsoCounts._fields_}
 
     def recvfrom(self, s, maxlen: int = 2048):
         buf = C.create_string_buffer(maxlen)
@@ -1596,6 +1763,17 @@ class HostApi:
         if rc != 0:
             raise UdpdkError(f"udpdk_tx_drain errno={self.errno()}")
         return [bytes(out[off[i]:off[i] + ln[i]]) for i in range(n.value)]
+
+    def tx_drain_raw(self, max_frames=4096, cap=1 << 22):
+        """udpdk_tx_drain as it answers: (out[cap] pre-filled with 0xEE, out_off[n], out_len[n])."""
+        out = np.full(cap, 0xEE, np.uint8)
+        off = np.zeros(max(1, max_frames), np.uint32)
+        ln = np.zeros(max(1, max_frames), np.uint16)
+        n = C.c_uint32()
+        rc = self.L.udpdk_tx_drain(_ptr(out), cap, _ptr(off), _ptr(ln), max_frames, C.byref(n))
+        if rc != 0:
+            raise UdpdkError(f"udpdk_tx_drain errno={self.errno()}")
+        return out, off[:n.value].copy(), ln[:n.value].copy()
 
     def poll_echo(self, frames: np.ndarray, frames_bytes: int, offset: np.ndarray, length: np.ndarray,
                   ptype: np.ndarray | None = None, max_frames=4096, cap=1 << 22):

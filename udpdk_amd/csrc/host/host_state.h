@@ -73,6 +73,7 @@ struct h_txd {                   /* one sendto waiting for the poller's TX half 
     uint32_t len;
     uint32_t dst_ip;             /* raw */
     uint32_t dst_port;           /* raw */
+    uint32_t gso;                /* segment size the drain cuts it at (UDP_SEGMENT), 0: one datagram */
 };
 
 struct h_txq {                   /* per-socket TX ring (exch_slots[s].tx_q, EXCH_RING_SIZE)      */
@@ -94,6 +95,7 @@ struct h_slot {                  /* exch_slot_info (udpdk_types.h:40-47) + bind 
     uint16_t peer_port;          /* raw */
     uint32_t peer_ip;            /* raw */
     atomic_int so_error;         /* pending ICMP error (udpdk_sock_error_post): an errno, 0 = none     */
+    uint16_t gso_size;           /* UDP_SEGMENT socket option: segment size of later sends, 0 = off   */
     uint8_t  n_mc;               /* groups joined (IP_ADD_MEMBERSHIP), raw addresses, in no order       */
     uint32_t mc_group[H_MCAST_MAX];
     struct h_ring rx;
@@ -245,8 +247,9 @@ struct h_state {
     /* TX work buffers (tx_drain), grow-only: host pinned staging + device */
     void     *tx_h, *tx_d, *tx_fr_d;
     uint64_t  tx_h_cap, tx_d_cap, tx_fr_d_cap;
-    struct h_txsel { int32_t s; uint32_t nf; uint64_t foff; } *tx_sel;
+    struct h_txsel { int32_t s; uint32_t nf; uint64_t foff; } *tx_sel;   /* nf, foff: of the whole send */
     uint64_t  tx_sel_cap;
+    udpdk_gso_counts_t gso_counts;               /* segmented sends (udpdk_gso_counts), under tx_lock */
     /* udpdk_poll_echo work buffers (rx_echo.c), grow-only: pinned staging of the batch, its device
      * copy, the device lanes + reply plan, the built replies, the pinned readback of the plan */
     void     *ec_h, *ec_in_d, *ec_ws_d, *ec_out_d, *ec_rb_h;

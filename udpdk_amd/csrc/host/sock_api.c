@@ -8,6 +8,10 @@
  * the poller's TX fragmentation carries (the reference writes past its 2048-byte mbuf above
  * 2006 bytes, §8 Q14); larger ones get EMSGSIZE.
  *
+ * Beyond the reference: udpdk_sendmsg and the UDP_SEGMENT socket option and control message
+ * (udpdk_api.h). Every send call ends in h_send_queue; a send with a segment size in force and more
+ * bytes than one segment is one ring entry with its size, cut on the GPU by udpdk_tx_drain.
+ *
  * sendto does what the reference's sendto does short of building the frame: validate, auto-bind,
  * queue the datagram on the socket's TX ring (ENOBUFS when full, :356-365). The frame is built
  * on the GPU by the poller's TX half (udpdk_tx_drain). recvfrom pops the socket's RX ring and
@@ -18,6 +22,7 @@
 #include <sched.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/uio.h>
 
 #include "host_state.h"
 
@@ -247,6 +252,7 @@ void h_tx_reset(void)
     g_udpdk.txp_bytes = g_udpdk.txp_cap = 0;
     g_udpdk.tx_queued = 0;
     g_udpdk.tx_dropped = 0;
+    memset(&g_udpdk.gso_counts, 0, sizeof(g_udpdk.gso_counts));
     pthread_mutex_unlock(&g_udpdk.tx_lock);
 }
 
@@ -266,6 +272,15 @@ uint64_t udpdk_tx_dropped(void)
     return q;
 }
 
+int udpdk_gso_counts(udpdk_gso_counts_t *counts)
+{
+    if (!counts) { errno = EINVAL; return -1; }
+    pthread_mutex_lock(&g_udpdk.tx_lock);
+    *counts = g_udpdk.gso_counts;
+    pthread_mutex_unlock(&g_udpdk.tx_lock);
+    return 0;
+}
+
 void h_sockets_reset(void)
 {
     for (int s = 0; s < UDPDK_MAX_SOCKETS; s++) {
@@ -280,6 +295,7 @@ void h_sockets_reset(void)
     g_udpdk.txp_bytes = g_udpdk.txp_cap = 0;
     g_udpdk.tx_queued = 0;
     g_udpdk.tx_dropped = 0;
+    memset(&g_udpdk.gso_counts, 0, sizeof(g_udpdk.gso_counts));
     __atomic_store_n(&g_udpdk.rx_nobufs, 0, __ATOMIC_RELAXED);   /* per library session */
     __atomic_store_n(&g_udpdk.rx_dropped, 0, __ATOMIC_RELAXED);
     __atomic_store_n(&g_udpdk.rx_balanced, 0, __ATOMIC_RELAXED);
@@ -310,6 +326,7 @@ int udpdk_socket(int domain, int type, int protocol)
             sl->ip = 0;
             sl->udp_port = 0;
             sl->connected = 0;
+            sl->gso_size = 0;
             sl->n_mc = 0;
             atomic_store(&sl->so_error, 0);
             sl->prev = sl->next = -1;
@@ -332,8 +349,28 @@ static int h_sockopt_check(int s, int level, int optname, const void *optval, co
     return 0;
 }
 
+/* IPPROTO_UDP / UDP_SEGMENT of a socket in use: the segment size of the socket's later sends (any
+ * other option of that level keeps the answer every unknown level gets, EINVAL). set: optval is the
+ * new value, else it receives the stored one. */
+static int h_udp_sockopt(int s, void *optval, socklen_t *optlen, int set)
+{
+    if (!optval || !optlen) { errno = EFAULT; return -1; }
+    if (set) {
+        if (*optlen < sizeof(int)) { errno = EINVAL; return -1; }
+        const int v = *(const int *)optval;
+        if (v < 0 || v > 65535) { errno = EINVAL; return -1; }
+        g_udpdk.slots[s].gso_size = (uint16_t)v;
+        return 0;
+    }
+    *(int *)optval = g_udpdk.slots[s].gso_size;
+    *optlen = sizeof(int);
+    return 0;
+}
+
 int udpdk_getsockopt(int s, int level, int optname, void *optval, socklen_t *optlen)
 {
+    if (level == IPPROTO_UDP && optname == UDP_SEGMENT && h_valid_fd(s) && g_udpdk.slots[s].used)
+        return h_udp_sockopt(s, optval, optlen, 0);
     if (optname == SO_ERROR && level == SOL_SOCKET && h_valid_fd(s) && g_udpdk.slots[s].used) {
         /* the pending ICMP error (udpdk_config_icmp_errors), cleared by the read; 0: none */
         if (!optval || !optlen) { errno = EFAULT; return -1; }
@@ -352,6 +389,8 @@ int udpdk_setsockopt(int s, int level, int optname, const void *optval, socklen_
 {
     /* IP_ADD_MEMBERSHIP / IP_DROP_MEMBERSHIP (mcast.c); any other IPPROTO_IP option: ENOPROTOOPT */
     if (level == IPPROTO_IP && h_valid_fd(s) && g_udpdk.slots[s].used) return h_mcast_sockopt(s, optname, optval, optlen);
+    if (level == IPPROTO_UDP && optname == UDP_SEGMENT && h_valid_fd(s) && g_udpdk.slots[s].used)
+        return h_udp_sockopt(s, (void *)optval, &optlen, 1);
     if (h_sockopt_check(s, level, optname, optval, &optlen)) return -1;
     struct h_slot *sl = &g_udpdk.slots[s];
     const int was = sl->so_options & optname;
@@ -418,6 +457,7 @@ int udpdk_close(int s)
     sl->bound = 0;
     sl->used = 0;
     sl->so_options = 0;
+    sl->gso_size = 0;
     g_udpdk.n_active--;
     g_udpdk.version++;
     atomic_store(&sl->rx.closing, 0);          /* later calls see used == 0 */
@@ -451,13 +491,18 @@ static int h_peer_locked(int s, struct sockaddr_in *a)
     return 1;
 }
 
-ssize_t udpdk_sendto(int s, const void *buf, size_t len, int flags,
-                     const struct sockaddr *dest, socklen_t addrlen)
+/* What every send call ends in: the payload is the iovecs gathered in order, gso the segment size a
+ * control message gave (-1: the socket's), bad_cmsg whether the control messages were refused
+ * (reported where Linux reports it, after the pending error). Validates, auto-binds and queues one
+ * ring entry; returns the payload's length or -1 with errno. */
+static ssize_t h_send_queue(int s, const struct iovec *iov, size_t iovcnt, int flags, const struct sockaddr *dest,
+                            socklen_t addrlen, int gso, int bad_cmsg)
 {
     if (s < 0 || s >= UDPDK_MAX_SOCKETS) { errno = ENOTSOCK; return -1; }
     if (!g_udpdk.slots[s].used) { errno = EBADF; return -1; }
     if (flags != 0) { errno = EINVAL; return -1; }
     { const int e = h_sock_error_take(s); if (e) { errno = e; return -1; } }   /* pending ICMP error */
+    if (bad_cmsg) { errno = EINVAL; return -1; }
     struct sockaddr_in peer;
     if (!dest) {
         /* a connected socket's peer (udpdk_connect); unconnected: EINVAL as ever */
@@ -469,8 +514,24 @@ ssize_t udpdk_sendto(int s, const void *buf, size_t len, int flags,
         addrlen = sizeof(peer);
     }
     if (addrlen == 0) { errno = EINVAL; return -1; }
+    if (iovcnt && !iov) { errno = EFAULT; return -1; }
+    uint64_t len = 0;
+    for (size_t i = 0; i < iovcnt; i++) {
+        len += iov[i].iov_len < (1u << 20) ? iov[i].iov_len : (1u << 20);    /* (anything above 65507 is too long) */
+        if (len > (1u << 20)) len = 1u << 20;
+    }
+    const uint32_t g = gso >= 0 ? (uint32_t)gso : g_udpdk.slots[s].gso_size;
+    if (g && (28u + g > g_udpdk.mtu || len > (uint64_t)g * UDPDK_GSO_MAX_SEGS)) {
+        /* udp_send_skb: a segment must fit the MTU, a send at most UDP_MAX_SEGMENTS segments */
+        pthread_mutex_lock(&g_udpdk.tx_lock);
+        g_udpdk.gso_counts.refused++;
+        pthread_mutex_unlock(&g_udpdk.tx_lock);
+        errno = EINVAL;
+        return -1;
+    }
     if (len > H_UDP_MAX_PAYLOAD) { errno = EMSGSIZE; return -1; }
-    if (len && !buf) { errno = EFAULT; return -1; }
+    for (size_t i = 0; i < iovcnt; i++)
+        if (iov[i].iov_len && !iov[i].iov_base) { errno = EFAULT; return -1; }
     pthread_mutex_lock(&g_udpdk.lock);
     const int rc = h_autobind_locked(s);
     pthread_mutex_unlock(&g_udpdk.lock);
@@ -498,8 +559,15 @@ ssize_t udpdk_sendto(int s, const void *buf, size_t len, int flags,
         t->len = (uint32_t)len;
         t->dst_ip = d->sin_addr.s_addr;
         t->dst_port = d->sin_port;
-        if (len) memcpy(g_udpdk.txp + g_udpdk.txp_bytes, buf, len);
-        g_udpdk.txp_bytes += len;
+        t->gso = g && len > g ? g : 0u;            /* (len <= g: an ordinary datagram) */
+        for (size_t i = 0; i < iovcnt; i++) {      /* stored once, contiguously */
+            if (iov[i].iov_len) memcpy(g_udpdk.txp + g_udpdk.txp_bytes, iov[i].iov_base, iov[i].iov_len);
+            g_udpdk.txp_bytes += iov[i].iov_len;
+        }
+        if (t->gso) {
+            g_udpdk.gso_counts.sends++;
+            g_udpdk.gso_counts.segments += (len + g - 1u) / g;
+        }
         q->tail++;
         g_udpdk.tx_queued++;
         ret = (ssize_t)len;
@@ -507,6 +575,35 @@ ssize_t udpdk_sendto(int s, const void *buf, size_t len, int flags,
 out:
     pthread_mutex_unlock(&g_udpdk.tx_lock);
     return ret;
+}
+
+ssize_t udpdk_sendto(int s, const void *buf, size_t len, int flags,
+                     const struct sockaddr *dest, socklen_t addrlen)
+{
+    const struct iovec v = {(void *)buf, len};
+    return h_send_queue(s, &v, 1, flags, dest, addrlen, -1, 0);
+}
+
+ssize_t udpdk_sendmsg(int s, const struct msghdr *msg, int flags)
+{
+    if (s < 0 || s >= UDPDK_MAX_SOCKETS) { errno = ENOTSOCK; return -1; }
+    if (!g_udpdk.slots[s].used) { errno = EBADF; return -1; }
+    if (!msg) { errno = EFAULT; return -1; }
+    /* the control messages: SOL_UDP / UDP_SEGMENT with a uint16_t is this call's segment size */
+    int gso = -1, bad = 0;
+    if (msg->msg_control && msg->msg_controllen) {
+        for (struct cmsghdr *c = CMSG_FIRSTHDR((struct msghdr *)msg); c; c = CMSG_NXTHDR((struct msghdr *)msg, c)) {
+            if (c->cmsg_level != SOL_UDP || c->cmsg_type != UDP_SEGMENT || c->cmsg_len != CMSG_LEN(sizeof(uint16_t))) {
+                bad = 1;
+                break;
+            }
+            uint16_t v;
+            memcpy(&v, CMSG_DATA(c), sizeof(v));
+            gso = v;
+        }
+    }
+    return h_send_queue(s, msg->msg_iov, msg->msg_iovlen, flags, msg->msg_name ? (const struct sockaddr *)msg->msg_name : NULL,
+                        msg->msg_name ? msg->msg_namelen : 0, gso, bad);
 }
 
 ssize_t udpdk_recvfrom(int s, void *buf, size_t len, int flags,

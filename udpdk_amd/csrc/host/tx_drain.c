@@ -21,6 +21,14 @@
  * dequeued and counted like the others the drain cannot send; its span in the output is a gap. The
  * requests go onto the host queue and leave first in the next drain. Off, the drain calls what it
  * always called.
+ *
+ * A send queued with a segment size (UDP_SEGMENT, sock_api.c) is selected as a unit: its frames and
+ * bytes come from udpdk_gpu_tx_segment_span, the burst counter advances by its frames, and the drop
+ * rule applies to the whole send. A drain that selected one stages the sends with their sizes instead
+ * of per-datagram frame offsets, and udpdk_gpu_tx_segment_plan expands them on the device into one
+ * descriptor per segment (max_segs = the host's own count) in front of the resolve and the build; the
+ * frame table comes from the closed form. A drain that selected none stages and launches what it
+ * always did.
  */
 #include <errno.h>
 #include <stdlib.h>
@@ -88,7 +96,7 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
     const uint32_t max_s = max - k0;
     const uint64_t cap_s = out_cap - b0;
     /* 1. selection in the poller's order */
-    uint32_t nsel = 0, nframes = 0, burst = 0;
+    uint32_t nsel = 0, nframes = 0, burst = 0, ndg = 0, n_gso = 0;   /* ndg: datagrams (a send's segments) */
     uint64_t bytes = 0, pay = 0;
     int progress = 1, full = 0;
     uint32_t taken[UDPDK_MAX_SOCKETS];
@@ -100,8 +108,8 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
             if (!g_udpdk.slots[s].used || !q->e) continue;
             while (burst < H_BURST_SIZE && q->head + taken[s] != q->tail) {
                 const struct h_txd *t = &q->e[(q->head + taken[s]) % UDPDK_RX_RING_SIZE];
-                uint32_t nf = 1;
-                const uint64_t span = udpdk_gpu_tx_span(t->len, mtu, &nf);
+                uint32_t nf = 1, nseg = 1;
+                const uint64_t span = udpdk_gpu_tx_segment_span(t->len, t->gso, mtu, &nseg, &nf);
                 if (nframes + nf > max_s || bytes + span > cap_s) {
                     if (nframes == 0 && taken[s] == 0 && (nf > max || span > out_cap)) {
                         /* larger than any drain with these limits can carry: it would block
@@ -126,6 +134,8 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
                 g_udpdk.tx_sel[nsel].nf = nf;
                 g_udpdk.tx_sel[nsel].foff = bytes;
                 nsel++;
+                ndg += nseg;
+                n_gso += t->gso != 0;
                 taken[s]++;
                 nframes += nf;
                 bytes += span;
@@ -143,18 +153,24 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
         goto out;
     }
     /* 2. host staging (pinned): payloads packed, then the per-datagram arrays */
+    /* (with a segmented send: its size in place of the frame offset, which the plan computes, and
+     * behind the staged bytes, device only, the plan's arrays: one descriptor per segment, frame_off,
+     * seg_off) */
     const uint64_t o_pay = 0, o_poff = a16(pay), o_len = o_poff + a16(4ull * nsel),
                    o_sock = o_len + a16(2ull * nsel), o_ip = o_sock + a16(4ull * nsel),
                    o_port = o_ip + a16(4ull * nsel), o_foff = o_port + a16(2ull * nsel),
-                   tot = o_foff + a16(4ull * nsel);
+                   tot = o_foff + a16(n_gso ? 2ull * nsel : 4ull * nsel);
+    const uint64_t p_poff = tot, p_len = p_poff + a16(4ull * ndg), p_sock = p_len + a16(2ull * ndg),
+                   p_ip = p_sock + a16(4ull * ndg), p_port = p_ip + a16(4ull * ndg), p_foff = p_port + a16(2ull * ndg),
+                   p_soff = p_foff + a16(4ull * ndg + 4), p_tot = p_soff + a16(4ull * nsel + 4);
     if (h_grow_pinned(&g_udpdk.tx_h, &g_udpdk.tx_h_cap, tot) ||
-        h_grow_dev(&g_udpdk.tx_d, &g_udpdk.tx_d_cap, tot + 64) ||
+        h_grow_dev(&g_udpdk.tx_d, &g_udpdk.tx_d_cap, (n_gso ? p_tot : tot) + 64) ||
         h_grow_dev(&g_udpdk.tx_fr_d, &g_udpdk.tx_fr_d_cap, bytes + 64))
         goto out;
     uint8_t *h = g_udpdk.tx_h;
     uint32_t *poff = (uint32_t *)(h + o_poff), *sock = (uint32_t *)(h + o_sock);
     uint32_t *ip = (uint32_t *)(h + o_ip), *foff = (uint32_t *)(h + o_foff);
-    uint16_t *len = (uint16_t *)(h + o_len), *port = (uint16_t *)(h + o_port);
+    uint16_t *len = (uint16_t *)(h + o_len), *port = (uint16_t *)(h + o_port), *gsz = (uint16_t *)(h + o_foff);
     memset(taken, 0, sizeof(taken));
     uint64_t pp = 0;
     for (uint32_t i = 0; i < nsel; i++) {
@@ -167,7 +183,8 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
         sock[i] = (uint32_t)s;
         ip[i] = t->dst_ip;
         port[i] = (uint16_t)t->dst_port;
-        foff[i] = (uint32_t)g_udpdk.tx_sel[i].foff;
+        if (n_gso) gsz[i] = (uint16_t)t->gso;
+        else foff[i] = (uint32_t)g_udpdk.tx_sel[i].foff;
         pp += t->len;
     }
     /* 3. GPU: one H2D, the build, one D2H */
@@ -181,12 +198,34 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
                           (const uint16_t *)(d + o_port), nsel};
     udpdk_tx_out_t o = {g_udpdk.tx_fr_d, bytes + 64, (const uint32_t *)(d + o_foff)};
     const int32_t *sock_out = NULL;
+    /* what the resolve and the build see: the staged datagrams, or the plan's segments */
+    const uint32_t *ip_d = (const uint32_t *)(d + o_ip);
+    const int32_t *sock_d = (const int32_t *)(d + o_sock);
+    if (n_gso) {
+        const udpdk_tx_sends_t sd = {d + o_pay, pay, (const uint32_t *)(d + o_poff), (const uint16_t *)(d + o_len),
+                                     (const uint16_t *)(d + o_foff), (const int32_t *)(d + o_sock),
+                                     (const uint32_t *)(d + o_ip), (const uint16_t *)(d + o_port), nsel};
+        const udpdk_tx_segment_plan_t pl = {(uint32_t *)(d + p_poff), (uint16_t *)(d + p_len), (int32_t *)(d + p_sock),
+                                            (uint32_t *)(d + p_ip), (uint16_t *)(d + p_port), (uint32_t *)(d + p_foff),
+                                            (uint32_t *)(d + p_soff), ndg};
+        if ((rc = udpdk_gpu_h2d(g, d, h, tot)) || (rc = udpdk_gpu_tx_segment_plan(g, &sd, mtu, 0u, bytes, &pl))) {
+            errno = -rc;
+            goto out;
+        }
+        g_udpdk.gso_counts.plans++;
+        const udpdk_tx_batch_t bp = {d + o_pay, pay, pl.payload_off_dev, pl.payload_len_dev, pl.sockfd_dev,
+                                     pl.dst_ip_dev, pl.dst_port_dev, ndg};
+        b = bp;
+        o.frame_off_dev = pl.frame_off_dev;
+        ip_d = pl.dst_ip_dev;
+        sock_d = pl.sockfd_dev;
+    }
     if (neigh) {
         /* device: MACs, resolved sockets, states, request slots, origins; pinned: sockets, slots */
-        const uint64_t n_mac = 0, n_sock = a16(8ull * nsel), n_state = n_sock + a16(4ull * nsel),
-                       n_req = n_state + a16(nsel), n_org = n_req + (uint64_t)H_NEIGH_REQ_CAP * UDPDK_ARP_SLOT_BYTES,
+        const uint64_t n_mac = 0, n_sock = a16(8ull * ndg), n_state = n_sock + a16(4ull * ndg),
+                       n_req = n_state + a16(ndg), n_org = n_req + (uint64_t)H_NEIGH_REQ_CAP * UDPDK_ARP_SLOT_BYTES,
                        n_tot = n_org + 4ull * H_NEIGH_REQ_CAP;
-        const uint64_t hq = a16(4ull * nsel), first = (uint64_t)H_NEIGH_REQ_FIRST * UDPDK_ARP_SLOT_BYTES;
+        const uint64_t hq = a16(4ull * ndg), first = (uint64_t)H_NEIGH_REQ_FIRST * UDPDK_ARP_SLOT_BYTES;
         if (h_neigh_table() || h_grow_dev(&g_udpdk.ng_d, &g_udpdk.ng_d_cap, n_tot) ||
             h_grow_pinned(&g_udpdk.ng_h, &g_udpdk.ng_h_cap, hq + (uint64_t)H_NEIGH_REQ_CAP * UDPDK_ARP_SLOT_BYTES))
             goto out;
@@ -197,12 +236,11 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
                                       (uint32_t *)(nd + n_org), H_NEIGH_REQ_CAP};
         udpdk_neigh_resolve_stats_t nst;
         b.sockfd_dev = no.sockfd_out_dev;
-        if ((rc = udpdk_gpu_h2d(g, d, h, tot)) ||
-            (rc = udpdk_gpu_neigh_resolve(g, &ncfg, (const uint32_t *)(d + o_ip), (const int32_t *)(d + o_sock), nsel,
-                                          h_neigh_now(), &no)) ||
+        if ((!n_gso && (rc = udpdk_gpu_h2d(g, d, h, tot))) ||
+            (rc = udpdk_gpu_neigh_resolve(g, &ncfg, ip_d, sock_d, ndg, h_neigh_now(), &no)) ||
             (rc = udpdk_gpu_tx_build_neigh(g, &cfg, &b, &o, mtu, txf, no.dmac_dev)) ||
             (rc = udpdk_gpu_d2h(g, out + b0, g_udpdk.tx_fr_d, bytes)) ||
-            (rc = udpdk_gpu_d2h(g, nh, no.sockfd_out_dev, 4ull * nsel)) ||
+            (rc = udpdk_gpu_d2h(g, nh, no.sockfd_out_dev, 4ull * ndg)) ||
             (rc = udpdk_gpu_d2h(g, nh + hq, no.req_dev, first))) {
             errno = -rc;
             goto out;
@@ -223,24 +261,34 @@ int udpdk_tx_drain(uint8_t *out, uint64_t out_cap, uint32_t *out_off, uint16_t *
                 g_udpdk.neigh_counts.requests++;
         h_neigh_count_resolve(&nst);
         sock_out = (const int32_t *)nh;
-    } else if ((rc = udpdk_gpu_h2d(g, d, h, tot)) || (rc = udpdk_gpu_tx_build_flags(g, &cfg, &b, &o, mtu, txf)) ||
+    } else if ((!n_gso && (rc = udpdk_gpu_h2d(g, d, h, tot))) || (rc = udpdk_gpu_tx_build_flags(g, &cfg, &b, &o, mtu, txf)) ||
         (rc = udpdk_gpu_d2h(g, out + b0, g_udpdk.tx_fr_d, bytes)) || (rc = udpdk_gpu_sync(g))) {
         errno = -rc;
         goto out;
     }
     /* 4. frame table, dequeue, payload store compaction */
-    uint32_t k = k0;
+    uint32_t k = k0, m = 0;
     for (uint32_t i = 0; i < nsel; i++) {
-        const uint32_t nf = g_udpdk.tx_sel[i].nf;
-        const uint64_t span = udpdk_gpu_tx_span(len[i], mtu, NULL);
-        if (sock_out && sock_out[i] < 0) {                  /* unresolved: nothing was built for it */
-            g_udpdk.neigh_counts.tx_unresolved++;
-            continue;
-        }
-        for (uint32_t f = 0; f < nf; f++) {
-            out_off[k] = (uint32_t)b0 + foff[i] + f * (mtu + 14u);
-            out_len[k] = (uint16_t)(f + 1 < nf ? mtu + 14u : span - (uint64_t)(nf - 1) * (mtu + 14u));
-            k++;
+        /* the send's segments by the closed form (one for an ordinary datagram), back to back */
+        const uint32_t gs = n_gso ? gsz[i] : 0u;
+        uint32_t nseg = 1;
+        udpdk_gpu_tx_segment_span(len[i], gs, mtu, &nseg, NULL);
+        uint64_t so = g_udpdk.tx_sel[i].foff;
+        for (uint32_t t = 0; t < nseg; t++, m++) {
+            const uint32_t sl = nseg > 1 && t + 1 < nseg ? gs : len[i] - t * gs;
+            uint32_t nf = 1;
+            const uint64_t span = udpdk_gpu_tx_span(sl, mtu, &nf);
+            const uint64_t fo = so;
+            so += span;
+            if (sock_out && sock_out[m] < 0) {              /* unresolved: nothing was built for it */
+                g_udpdk.neigh_counts.tx_unresolved++;
+                continue;
+            }
+            for (uint32_t f = 0; f < nf; f++) {
+                out_off[k] = (uint32_t)(b0 + fo) + f * (mtu + 14u);
+                out_len[k] = (uint16_t)(f + 1 < nf ? mtu + 14u : span - (uint64_t)(nf - 1) * (mtu + 14u));
+                k++;
+            }
         }
     }
     for (int s = 0; s < UDPDK_MAX_SOCKETS; s++) g_udpdk.slots[s].tx.head += taken[s];

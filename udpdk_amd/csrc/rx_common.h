@@ -481,4 +481,53 @@ __global__ void tx_reply_desc(ReplyArgs a);
 __global__ void tx_reply_base(ReplyArgs a);
 __global__ void tx_reply_place(ReplyArgs a);
 
+// Segment plan (tx_segment.hip): K sends with a segment size -> the descriptor arrays of a
+// udpdk_tx_batch_t with one entry per segment (UDP_SEGMENT on the device).
+constexpr int      SEG_BLOCK = 256;          // one send (rows, place) or one segment (expand) per lane
+constexpr uint32_t SEG_SEND_TILE = SEG_BLOCK;    // sends per workgroup (udpdk_gpu_tx_segment_geometry)
+constexpr uint32_t SEG_TILE = SEG_BLOCK;         // segments per workgroup
+constexpr int      SEG_BASE_BLOCK = 256;     // tx_segment_base: one workgroup, a run of rows per lane
+// per-workgroup row: output bytes, segments, output frames, sends with segments, and the sends
+// skipped for a negative sockfd, their length, their range, their segment count
+constexpr uint32_t SEG_ROW = 8;
+enum { SEG_R_BYTES = 0, SEG_R_NSEG = 1, SEG_R_FRAMES = 2, SEG_R_OK = 3, SEG_R_SKIPPED = 4, SEG_R_TOO_LONG = 5,
+       SEG_R_BAD_RANGE = 6, SEG_R_TOO_MANY = 7 };
+
+// the device image of udpdk_tx_segment_stats_t, where the output ends (frame_off[N]) and the first
+// send out of room (k when there is none)
+struct SegResult {
+    unsigned long long bytes_needed, segs_needed, end;
+    uint32_t sends, segments, frames, skipped, too_long, bad_range, too_many, no_room;
+    uint32_t cut_send, pad;
+};
+
+struct SegArgs {
+    const uint32_t *s_payload_off; // [k] the sends
+    const uint16_t *s_payload_len;
+    const uint16_t *s_gso;
+    const int32_t  *s_sockfd;
+    const uint32_t *s_dst_ip;
+    const uint16_t *s_dst_port;
+    uint32_t *payload_off;         // [max_segs] the segments
+    uint16_t *payload_len;
+    int32_t  *sockfd;
+    uint32_t *dst_ip;
+    uint16_t *dst_port;
+    uint32_t *frame_off;           // [max_segs + 1]
+    uint32_t *seg_off;             // [k + 1]
+    uint32_t *send_base;           // [k] where a send's frames start (tx_segment_place)
+    uint32_t *row;                 // [SEG_ROW][n_blocks], field-major (tx_segment_rows)
+    unsigned long long *base;      // [2][n_blocks] output bytes, then segments, before the workgroup
+    SegResult *res;
+    uint32_t k, max_segs;
+    uint32_t payload_bytes;
+    uint32_t mtu, seg_limit;
+    uint32_t out_cap;
+    uint32_t n_blocks;             // ceil(k / SEG_SEND_TILE)
+};
+__global__ void tx_segment_rows(SegArgs a);
+__global__ void tx_segment_base(SegArgs a);
+__global__ void tx_segment_place(SegArgs a);
+__global__ void tx_segment_expand(SegArgs a);
+
 } // namespace udpdk

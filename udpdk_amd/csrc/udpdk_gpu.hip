@@ -160,6 +160,14 @@ struct ReplyWs {
     void release() { release_all(row, base, res); }
 };
 
+// Workspace of the segment plan (tx_segment.hip), lazily sized; one per context (the context stream).
+struct SegWs {
+    DevBuf<uint32_t> row, send_base;
+    DevBuf<unsigned long long> base;
+    ResultSlot<SegResult> res;
+    void release() { release_all(row, send_base, base, res); }
+};
+
 // Workspace of the ICMP reply stage (icmp_reply.hip), lazily sized by the context's max_frames: one
 // for the context stream (udpdk_gpu_icmp_reply) and one per pipe (udpdk_gpu_pipe_icmp_reply).
 struct IcmpWs {
@@ -322,6 +330,7 @@ struct udpdk_gpu_ctx {
     FilterWs xmcast;                          // explicit udpdk_gpu_rx_mcast_select calls
     FilterWs *mcast_last = nullptr;           // the last membership filter run (udpdk_gpu_rx_mcast_stats)
     ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
+    SegWs seg;                                // udpdk_gpu_tx_segment_plan / udpdk_gpu_tx_segment
     IcmpWs icmp;                              // udpdk_gpu_icmp_reply (the context stream)
     IcmpErrWs icmp_err;                       // udpdk_gpu_icmp_errors (the context stream)
     ArpWs arp;                                // udpdk_gpu_arp_reply (the context stream)
@@ -357,7 +366,7 @@ struct udpdk_gpu_ctx {
     {
         for (Pipe &P : pipes) P.release();
         release_all(port_tab, binds, slots, hint, xflt, bal_rp, bal_ktab, xbal, peer_tab, xpeer, mcast_mc, mcast_tab,
-                    xmcast, rpl, icmp,
+                    xmcast, rpl, seg, icmp,
                     icmp_err, arp, igmp, neigh_tab, nlearn, nresolve, rss_reta, rss_ktab, rss_qid, rss_hist, rss_partial, rss_total, rss_fuse);
     }
 };
@@ -2222,6 +2231,149 @@ int udpdk_gpu_tx_reply_stats(udpdk_gpu_ctx *c, udpdk_tx_reply_stats_t *st)
     st->unselected = r->unselected;
     st->no_room = r->no_room;
     st->frames = r->frames;
+    return st->no_room ? -ENOSPC : 0;
+}
+
+namespace {
+
+// Argument checks shared by udpdk_gpu_tx_segment_plan and udpdk_gpu_tx_segment: nothing is enqueued
+// unless all pass.
+int segment_check(const udpdk_gpu_ctx *c, const udpdk_tx_sends_t *sd, uint32_t mtu, uint64_t out_cap,
+                  const udpdk_tx_segment_plan_t *pl)
+{
+    if (!c || !sd || !pl) return -EINVAL;
+    if (mtu && (mtu < 68u || mtu > 65535u || (mtu - 20u) % 8u)) return -EINVAL;
+    if (sd->payload_bytes >= (1ull << 32) || out_cap >= (1ull << 32)) return -EINVAL;
+    if (pl->max_segs == 0 || (uint64_t)sd->k + pl->max_segs >= (1ull << 32)) return -EINVAL;
+    if (!sd->payload_dev || !sd->payload_off_dev || !sd->payload_len_dev || !sd->gso_size_dev || !sd->sockfd_dev ||
+        !sd->dst_ip_dev || !sd->dst_port_dev) return -EINVAL;
+    if (!pl->payload_off_dev || !pl->payload_len_dev || !pl->sockfd_dev || !pl->dst_ip_dev || !pl->dst_port_dev ||
+        !pl->frame_off_dev || !pl->seg_off_dev) return -EINVAL;
+    return 0;
+}
+
+// The segment plan (tx_segment.hip) on the context stream: rows, base, placement, expansion.
+int segment_enqueue(udpdk_gpu_ctx *c, const udpdk_tx_sends_t *sd, uint32_t mtu, uint32_t seg_limit,
+                    uint64_t out_cap, const udpdk_tx_segment_plan_t *pl)
+{
+    SegWs &W = c->seg;
+    const uint32_t nb = ceil_div(sd->k, SEG_SEND_TILE);
+    int rc;
+    if ((rc = W.row.ensure(c, (size_t)nb * SEG_ROW)) || (rc = W.base.ensure(c, 2u * (size_t)nb)) ||
+        (rc = W.send_base.ensure(c, sd->k)) || (rc = W.res.ensure(c))) return rc;
+    SegArgs sa;
+    sa.s_payload_off = sd->payload_off_dev;
+    sa.s_payload_len = sd->payload_len_dev;
+    sa.s_gso = sd->gso_size_dev;
+    sa.s_sockfd = sd->sockfd_dev;
+    sa.s_dst_ip = sd->dst_ip_dev;
+    sa.s_dst_port = sd->dst_port_dev;
+    sa.payload_off = pl->payload_off_dev;
+    sa.payload_len = pl->payload_len_dev;
+    sa.sockfd = pl->sockfd_dev;
+    sa.dst_ip = pl->dst_ip_dev;
+    sa.dst_port = pl->dst_port_dev;
+    sa.frame_off = pl->frame_off_dev;
+    sa.seg_off = pl->seg_off_dev;
+    sa.send_base = W.send_base;
+    sa.row = W.row;
+    sa.base = W.base;
+    sa.res = W.res.dev;
+    sa.k = sd->k;
+    sa.max_segs = pl->max_segs;
+    sa.payload_bytes = (uint32_t)sd->payload_bytes;
+    sa.mtu = mtu;
+    sa.seg_limit = seg_limit;
+    sa.out_cap = (uint32_t)out_cap;
+    sa.n_blocks = nb;
+    hipLaunchKernelGGL(tx_segment_rows, dim3(nb), dim3(SEG_BLOCK), 0, c->stream, sa);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(tx_segment_base, dim3(1), dim3(SEG_BASE_BLOCK), 0, c->stream, sa);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(tx_segment_place, dim3((uint32_t)(((uint64_t)sd->k + SEG_SEND_TILE) / SEG_SEND_TILE)),
+                       dim3(SEG_BLOCK), 0, c->stream, sa);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(tx_segment_expand, dim3((uint32_t)(((uint64_t)pl->max_segs + SEG_TILE) / SEG_TILE)),
+                       dim3(SEG_BLOCK), 0, c->stream, sa);
+    HIPC(c, hipGetLastError());
+    W.res.ran = true;
+    return 0;
+}
+
+} // namespace
+
+uint64_t udpdk_gpu_tx_segment_span(uint32_t len, uint32_t gso, uint32_t mtu, uint32_t *nseg, uint32_t *n_frames)
+{
+    uint32_t ns = 1, nf = 0;
+    uint64_t span;
+    if (gso == 0 || len <= gso) {
+        span = udpdk_gpu_tx_span(len, mtu, &nf);
+    } else {
+        const uint32_t q = len / gso, r = len % gso;
+        uint32_t fq = 0, fr = 0;
+        span = (uint64_t)q * udpdk_gpu_tx_span(gso, mtu, &fq) + (r ? udpdk_gpu_tx_span(r, mtu, &fr) : 0);
+        ns = q + (r != 0);
+        nf = q * fq + fr;
+    }
+    if (nseg) *nseg = ns;
+    if (n_frames) *n_frames = nf;
+    return span;
+}
+
+int udpdk_gpu_tx_segment_geometry(uint32_t k, uint32_t max_segs, uint32_t *sends_per_block,
+                                  uint32_t *segs_per_block, uint32_t *send_blocks, uint32_t *seg_blocks)
+{
+    if (!sends_per_block || !segs_per_block || !send_blocks || !seg_blocks) return -EINVAL;
+    *sends_per_block = SEG_SEND_TILE;
+    *segs_per_block = SEG_TILE;
+    *send_blocks = std::max<uint32_t>(1u, ceil_div(k, SEG_SEND_TILE));
+    *seg_blocks = std::max<uint32_t>(1u, ceil_div(max_segs, SEG_TILE));
+    return 0;
+}
+
+int udpdk_gpu_tx_segment_plan(udpdk_gpu_ctx *c, const udpdk_tx_sends_t *sd, uint32_t mtu, uint32_t seg_limit,
+                              uint64_t out_cap, const udpdk_tx_segment_plan_t *pl)
+{
+    int rc = segment_check(c, sd, mtu, out_cap, pl);
+    if (rc || !sd->k) return rc;
+    if ((rc = on_ctx_stream(c))) return rc;
+    return segment_enqueue(c, sd, mtu, seg_limit, out_cap, pl);
+}
+
+int udpdk_gpu_tx_segment(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_tx_sends_t *sd, uint32_t mtu,
+                         uint32_t flags, uint32_t seg_limit, uint8_t *frames_out_dev, uint64_t out_cap,
+                         const udpdk_tx_segment_plan_t *pl)
+{
+    if (!cfg || !frames_out_dev || (flags & ~UDPDK_TX_UDP_CKSUM)) return -EINVAL;
+    int rc = segment_check(c, sd, mtu, out_cap, pl);
+    if (rc) return rc;
+    if (((uintptr_t)frames_out_dev & 15u) || ((uintptr_t)sd->payload_dev & 15u)) return -EINVAL;
+    if (!c->slots || !c->n_slots) return -EINVAL;
+    if (!sd->k) return 0;
+    if ((rc = on_ctx_stream(c))) return rc;
+    if ((rc = segment_enqueue(c, sd, mtu, seg_limit, out_cap, pl))) return rc;
+    const udpdk_tx_batch_t tb = {sd->payload_dev, sd->payload_bytes, pl->payload_off_dev, pl->payload_len_dev,
+                                 pl->sockfd_dev, pl->dst_ip_dev, pl->dst_port_dev, pl->max_segs};
+    const udpdk_tx_out_t to = {frames_out_dev, out_cap, pl->frame_off_dev};
+    return udpdk_gpu_tx_build_flags(c, cfg, &tb, &to, mtu, flags);
+}
+
+int udpdk_gpu_tx_segment_stats(udpdk_gpu_ctx *c, udpdk_tx_segment_stats_t *st)
+{
+    if (!c || !st) return -EINVAL;
+    const int rc = ctx_result(c, c->seg.res);
+    if (rc) return rc;
+    const SegResult *r = c->seg.res.host;
+    st->bytes_needed = r->bytes_needed;
+    st->segs_needed = r->segs_needed;
+    st->sends = r->sends;
+    st->segments = r->segments;
+    st->frames = r->frames;
+    st->skipped = r->skipped;
+    st->too_long = r->too_long;
+    st->bad_range = r->bad_range;
+    st->too_many = r->too_many;
+    st->no_room = r->no_room;
     return st->no_room ? -ENOSPC : 0;
 }
 
