@@ -10,13 +10,13 @@ LIB       := udpdk_amd/libudpdk_amd.so
 OBJDIR    := build/obj
 
 HIP_SRC   := udpdk_amd/csrc/rx_classify.hip udpdk_amd/csrc/rx_lanes.hip udpdk_amd/csrc/rx_gather.hip udpdk_amd/csrc/rx_reasm.hip \
-             udpdk_amd/csrc/rx_rss.hip udpdk_amd/csrc/tx_kernels.hip udpdk_amd/csrc/tx_reply.hip udpdk_amd/csrc/tx_segment.hip udpdk_amd/csrc/rx_filter.hip udpdk_amd/csrc/rx_balance.hip udpdk_amd/csrc/rx_peer.hip udpdk_amd/csrc/rx_mcast.hip udpdk_amd/csrc/icmp_reply.hip udpdk_amd/csrc/icmp_error.hip udpdk_amd/csrc/arp_reply.hip udpdk_amd/csrc/igmp_reply.hip udpdk_amd/csrc/neigh.hip \
+             udpdk_amd/csrc/rx_rss.hip udpdk_amd/csrc/tx_kernels.hip udpdk_amd/csrc/tx_reply.hip udpdk_amd/csrc/tx_segment.hip udpdk_amd/csrc/rx_filter.hip udpdk_amd/csrc/rx_balance.hip udpdk_amd/csrc/rx_peer.hip udpdk_amd/csrc/rx_mcast.hip udpdk_amd/csrc/icmp_reply.hip udpdk_amd/csrc/icmp_error.hip udpdk_amd/csrc/arp_reply.hip udpdk_amd/csrc/igmp_reply.hip udpdk_amd/csrc/neigh.hip udpdk_amd/csrc/udpdk_gpu_ctl.hip \
              udpdk_amd/csrc/udpdk_gpu.hip
 C_SRC     := $(wildcard udpdk_amd/csrc/host/*.c)
 HIP_OBJ   := $(patsubst udpdk_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
 C_OBJ     := $(patsubst udpdk_amd/csrc/host/%.c,$(OBJDIR)/host/%.o,$(C_SRC))
 HDRS      := include/udpdk_gpu.h include/udpdk_api.h udpdk_amd/csrc/rx_common.h \
-             udpdk_amd/csrc/rx_plan.h udpdk_amd/csrc/rx_filter.h udpdk_amd/csrc/rx_balance.h udpdk_amd/csrc/rx_peer.h udpdk_amd/csrc/rx_mcast.h udpdk_amd/csrc/icmp_reply.h udpdk_amd/csrc/icmp_error.h udpdk_amd/csrc/arp_reply.h udpdk_amd/csrc/igmp_reply.h udpdk_amd/csrc/neigh.h udpdk_amd/csrc/tx_ipv4.h udpdk_amd/csrc/lane_find.h udpdk_amd/csrc/rss_toeplitz.h udpdk_amd/csrc/rss_host.h udpdk_amd/csrc/wave.h udpdk_amd/csrc/stamps.h $(wildcard udpdk_amd/csrc/host/*.h)
+             udpdk_amd/csrc/rx_plan.h udpdk_amd/csrc/rx_filter.h udpdk_amd/csrc/rx_balance.h udpdk_amd/csrc/rx_peer.h udpdk_amd/csrc/rx_mcast.h udpdk_amd/csrc/icmp_reply.h udpdk_amd/csrc/icmp_error.h udpdk_amd/csrc/arp_reply.h udpdk_amd/csrc/igmp_reply.h udpdk_amd/csrc/neigh.h udpdk_amd/csrc/tx_ipv4.h udpdk_amd/csrc/lane_find.h udpdk_amd/csrc/rss_toeplitz.h udpdk_amd/csrc/rss_host.h udpdk_amd/csrc/wave.h udpdk_amd/csrc/fanin_stage.h udpdk_amd/csrc/gpu_ctx.h udpdk_amd/csrc/stamps.h $(wildcard udpdk_amd/csrc/host/*.h)
 
 TOOLS     := tools/bin/bench_sock build/rx_plan_check build/rss_host_check build/echo_expand_check build/icmp_queue_check build/arp_frame_check build/igmp_frame_check
 

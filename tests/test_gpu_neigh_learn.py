@@ -104,6 +104,31 @@ def test_same_sender_in_the_first_and_the_last_workgroup(gpu_ctx):
     assert tab.as_map() == {U.raw("10.5.5.5"): (m[3], U.REACHABLE, 77), U.raw("10.6.6.6"): (m[1], U.REACHABLE, 77)}
 
 
+def test_more_than_256_workgroups(gpu_ctx):
+    """Past 256 workgroups the finishing workgroup holds several rows per lane, and an event's workgroup is found
+    by bisection across the lanes' runs. The descriptors alias a few frames (the stage only reads them), so the
+    batch is large in frames only: a new host asking for us at the first and last frame of some blocks and at the
+    last frame, UDP elsewhere. One address asks from block 0 and again, with another MAC, from block 512."""
+    rng = np.random.default_rng(59)
+    n = 2 * 256 * T + 77
+    at = sorted({p for blk in (0, 1, 255, 256, 257, 300, 510, 511, 512) for p in (blk * T, min(n, (blk + 1) * T) - 1)}
+                | {n - 1})
+    assert len(at) == 18 and at[-1] == n - 1 and at[-2] == 512 * T
+    reqs = [_request(rng, j) for j in range(len(at))]
+    m0, m1 = bytes.fromhex("02ee00000001"), bytes.fromhex("02ee00000002")
+    reqs[0] = A.arp_frame(sha=m0, spa=_ip(0), tpa=US)
+    reqs[at.index(512 * T)] = A.arp_frame(sha=m1, spa=_ip(0), tpa=US)                   # host 0 again, a new MAC
+    buf, nb, foff, fln = A.pack([A.udp_frame(rng, payload_len=18)] + reqs, aligns=[j % 16 for j in range(1 + len(at))])
+    which = np.zeros(n, np.int64)                                  # 0: the UDP frame
+    which[at] = 1 + np.arange(len(at))
+    off, ln = foff[which], fln[which]
+    meta = np.where(which > 0, A.V_NOT_IPV4, abi.V_DELIVERED).astype(np.uint32)
+    tab = _setup(gpu_ctx, 64)
+    R = _check(gpu_ctx, tab, (buf, nb, off, ln), meta, 4000)
+    assert R["stats"] == dict({k: 0 for k in U.LEARN_FIELDS}, arp=len(at), created=len(at) - 1, updated=1)
+    assert tab.as_map()[U.raw(_ip(0))] == (m1, U.REACHABLE, 4000)
+
+
 def _every_class_batch(rng, n=1500):
     """Every learn class and every ARP kind of arp_util among UDP filler, frame k at offset == 5 k mod 16."""
     known = [_ip(200 + k) for k in range(8)]                       # REACHABLE in the table

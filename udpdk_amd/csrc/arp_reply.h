@@ -1,5 +1,5 @@
 // arp_reply.h — launch constants, workspace rows and the argument block shared by the ARP reply
-// kernel (arp_reply.hip) and the C-ABI host code (udpdk_gpu.hip). Device-internal.
+// kernel (arp_reply.hip) and the C-ABI host code (udpdk_gpu_ctl.hip). Device-internal.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,7 +38,7 @@ struct ArpArgs {
     ArpEntry *cand;                // [n_blocks x ARP_TILE]
     uint32_t *row;                 // [ARP_ROW][n_blocks]
     uint32_t *rbase;               // [n_blocks] eligible requests before the workgroup
-    unsigned long long *fuse;      // fan-in words (fanin_arrive), zero between launches
+    unsigned long long *fuse;      // fan-in words (fanin_stage.h), zero between launches
     ArpResult *res;
     uint32_t n, n_blocks;
     uint32_t frames_bytes, rsrc_bytes;

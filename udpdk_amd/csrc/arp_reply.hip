@@ -27,12 +27,12 @@
 #include "rx_common.h"
 #include "arp_reply.h"
 #include "wave.h"
+#include "fanin_stage.h"
 
 namespace udpdk {
 
 namespace {
 
-constexpr uint32_t OOR = 0x80000000u;      // a buffer offset out of every range: no memory access, zeros
 constexpr int NW = ARP_BLOCK / 64;
 
 } // namespace

@@ -1,5 +1,5 @@
 // icmp_error.h — launch constants, the result block and the argument block shared by the ICMP error
-// kernels (icmp_error.hip) and the C-ABI host code (udpdk_gpu.hip). Device-internal.
+// kernels (icmp_error.hip) and the C-ABI host code (udpdk_gpu_ctl.hip). Device-internal.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

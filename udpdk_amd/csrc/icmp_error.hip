@@ -33,12 +33,12 @@
 #include "rx_common.h"
 #include "icmp_error.h"
 #include "wave.h"
+#include "fanin_stage.h"
 
 namespace udpdk {
 
 namespace {
 
-constexpr uint32_t OOR = 0x80000000u;      // a buffer offset out of every range: no memory access, zeros
 constexpr int NW = ICMP_ERR_BLOCK / 64;
 
 } // namespace
@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(ICMP_ERR_BLOCK)
 icmp_err_scan(IcmpErrArgs a)
 {
     __shared__ uint32_t red[NW][ICMP_ERR_ROW];
-    const uint32_t tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = lane_id();
     const uint64_t i64 = (uint64_t)blockIdx.x * ICMP_ERR_TILE + tid;
     const bool valid = i64 < a.n;
     const uint32_t i = (uint32_t)i64;
@@ -152,15 +152,10 @@ icmp_err_scan(IcmpErrArgs a)
         cnt[ICMP_X_REPORTED] = wave_sum(pairs);
         cnt[ICMP_X_BAD_FRAME] = (uint32_t)__popcll(__ballot(cand && !fok));
     }
-    if (lane == 0) {
-#pragma unroll
-        for (uint32_t k = 0; k < ICMP_ERR_ROW; ++k) red[w][k] = cnt[k];
-    }
+    wave_counts_put(red, cnt);
     __syncthreads();
     if (tid < ICMP_ERR_ROW) {
-        uint32_t t = 0u;
-#pragma unroll
-        for (int j = 0; j < NW; ++j) t += red[j][tid];
+        const uint32_t t = wave_counts_sum<NW>(red, tid);
         if (t) atomicAdd(&a.res->c[tid], t);
     }
 }

@@ -1,5 +1,5 @@
 // icmp_reply.h — launch constants, workspace rows and the argument block shared by the ICMP reply
-// kernels (icmp_reply.hip) and the C-ABI host code (udpdk_gpu.hip). Device-internal.
+// kernels (icmp_reply.hip) and the C-ABI host code (udpdk_gpu_ctl.hip). Device-internal.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

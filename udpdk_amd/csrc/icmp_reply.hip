@@ -39,13 +39,13 @@
 #include "rx_common.h"
 #include "icmp_reply.h"
 #include "wave.h"
+#include "fanin_stage.h"
 #include "tx_ipv4.h"
 
 namespace udpdk {
 
 namespace {
 
-constexpr uint32_t OOR = 0x80000000u;      // a buffer offset out of every range: no memory access, zeros
 constexpr int NW = ICMP_BLOCK / 64;
 
 __device__ __forceinline__ uint32_t sel4(uint32_t d, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3)
@@ -167,12 +167,7 @@ icmp_scan(IcmpArgs a)
         for (uint32_t j = 0; j < w; ++j) rank += wcnt[j];
         a.cand[(size_t)blockIdx.x * ICMP_TILE + rank] = ent;
     }
-    if (tid < ICMP_ROW) {
-        uint32_t t = 0u;
-#pragma unroll
-        for (int j = 0; j < NW; ++j) t += red[j][tid];
-        a.row[(size_t)tid * a.n_blocks + blockIdx.x] = t;           // field-major rows
-    }
+    row_store<NW, ICMP_ROW>(red, a.row + blockIdx.x, a.n_blocks);
 }
 
 // err_limit over the rows' eligible errors in arrival order, then the exclusive prefixes of what is

@@ -1,5 +1,5 @@
 // igmp_reply.h — launch constants, workspace rows and the argument block shared by the IGMP query
-// responder (igmp_reply.hip) and the C-ABI host code (udpdk_gpu.hip). Device-internal.
+// responder (igmp_reply.hip) and the C-ABI host code (udpdk_gpu_ctl.hip). Device-internal.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,7 +39,7 @@ struct IgmpQArgs {
     uint32_t *group_index;         // [max_reports]
     uint32_t *row;                 // [IGMP_ROW][n_blocks]
     uint32_t *bits;                // [IGMP_WORDS] the answer set, zero between launches
-    unsigned long long *fuse;      // fan-in words (fanin_arrive), zero between launches
+    unsigned long long *fuse;      // fan-in words (fanin_stage.h), zero between launches
     IgmpQResult *res;
     uint32_t n, n_blocks;
     uint32_t frames_bytes, rsrc_bytes;

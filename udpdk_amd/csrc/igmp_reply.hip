@@ -12,10 +12,10 @@
 //               range-checked buffer loads. A specific query that is to be answered finds its group
 //               by a linear search of groups_dev and sets the group's bit in the answer set; a
 //               general query only counts. The workgroup's row holds the counts.
-//               The launch's last workgroup to arrive (fanin_arrive) finishes: it sums the rows into
-//               the result, and only when a bit is set takes the prefix of the set bits (sixteen
-//               groups per lane) and writes the reports in index order, one lane per report, four
-//               aligned 16-byte stores of the 64-byte slot. It leaves the answer set zeroed.
+//               The launch's last workgroup to arrive finishes (fanin_stage.h): the row sums into the
+//               result, and only when a bit is set the prefix of the set bits (sixteen groups per
+//               lane) and the reports in index order, one lane per report, four aligned 16-byte
+//               stores of the 64-byte slot. It leaves the answer set zeroed.
 // One launch: no workgroup waits for another, and a batch without a candidate ends with the row sums.
 //
 // Bytes per frame: 4 (meta) + 36 / IGMP_TILE (row). Per candidate: + 6 (descriptor) + the 64-byte
@@ -27,12 +27,12 @@
 #include "rx_common.h"
 #include "igmp_reply.h"
 #include "wave.h"
+#include "fanin_stage.h"
 
 namespace udpdk {
 
 namespace {
 
-constexpr uint32_t OOR = 0xFFFFFFF0u;      // a buffer offset out of every range: no memory access, zeros
 constexpr int NW = IGMP_BLOCK / 64;
 
 // the four bytes at byte offset x of the frames buffer, any alignment: two dword loads
@@ -127,51 +127,13 @@ igmp_reply(IgmpQArgs a)
         cnt[IGMP_R_SPECIFIC] += (uint32_t)__popcll(__ballot(found));
         cnt[IGMP_R_BAD_FRAME] += (uint32_t)__popcll(__ballot(cand && !fok));
     }
-    if (lane == 0) {
-#pragma unroll
-        for (uint32_t f = 0; f < IGMP_ROW; ++f) red[w][f] = cnt[f];
-    }
+    wave_counts_put(red, cnt);
     __syncthreads();
-    if (tid < IGMP_ROW) {
-        uint32_t t = 0u;
-#pragma unroll
-        for (int j = 0; j < NW; ++j) t += red[j][tid];
-        a.row[(size_t)tid * nb + b] = t;                            // field-major rows
-    }
-    // the launch's last workgroup finishes: every wave's stores drained, one agent release, the arrival
-    stores_done();
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        stores_done();
-        unsigned long long fin;
-        s_last = fanin_arrive(a.fuse, b, nb, 0ull, &fin) ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    stores_done();
-    __syncthreads();
+    row_store<NW, IGMP_ROW>(red, a.row + b, nb);
+    if (!arrive_last<true>(a.fuse, b, nb, &s_last)) return;
 
-    // the counts
-    uint32_t acc[IGMP_ROW] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    for (uint32_t t = tid; t < nb; t += IGMP_BLOCK) {
-#pragma unroll
-        for (uint32_t f = 0; f < IGMP_ROW; ++f) acc[f] += a.row[(size_t)f * nb + t];
-    }
-#pragma unroll
-    for (uint32_t f = 0; f < IGMP_ROW; ++f) {
-        const uint32_t s = wave_sum(acc[f]);
-        if (lane == 0) red[w][f] = s;
-    }
-    __syncthreads();
-    if (tid < IGMP_ROW) {
-        uint32_t t = 0u;
-#pragma unroll
-        for (int j = 0; j < NW; ++j) t += red[j][tid];
-        tot[tid] = t;
-    }
-    __syncthreads();
+    // ---- the launch's last workgroup: the counts, then the reports ----
+    row_sums<IGMP_BLOCK, IGMP_ROW>(a.row, nb, red, tot);
     if (tid < IGMP_ROW) a.res->c[tid] = tot[tid];
     if (tot[IGMP_R_GENERAL] + tot[IGMP_R_SPECIFIC] == 0u) {         // (the whole workgroup: no bit is set)
         if (tid == 0) a.res->reports = a.res->no_room = 0u;
@@ -181,8 +143,7 @@ igmp_reply(IgmpQArgs a)
     // The answer set: groups [16 tid, 16 tid + 16) are this lane's, so the reports come out in index
     // order. A general query asks for every group but 224.0.0.1.
     const uint32_t g0 = tid * IGMP_PER_LANE;
-    uint32_t mine = (__hip_atomic_load(&a.bits[tid >> 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >>
-                     (16u * (tid & 1u))) & 0xFFFFu;
+    uint32_t mine = (agent_ld(&a.bits[tid >> 1]) >> (16u * (tid & 1u))) & 0xFFFFu;
     uint32_t grp[IGMP_PER_LANE];
 #pragma unroll
     for (uint32_t j = 0; j < IGMP_PER_LANE; ++j) grp[j] = g0 + j < a.n_groups ? a.groups[g0 + j] : 0u;
@@ -206,7 +167,7 @@ igmp_reply(IgmpQArgs a)
         a.res->no_room = total - reports;
     }
     // every lane has read its bits: the set goes back to zeros for the next launch
-    if (tid < IGMP_WORDS) __hip_atomic_store(&a.bits[tid], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid < IGMP_WORDS) agent_st(&a.bits[tid], 0u);
 
     const uint32_t D2 = (a.mac_lo >> 16) | (a.mac_hi << 16);        // our MAC bytes 2-5
 #pragma unroll

@@ -1,6 +1,6 @@
 // neigh.h — the neighbour table's layout and hash, the destination classes (rules R1-R4 of
 // udpdk_gpu_neigh_resolve, one statement for the kernel and the host), launch constants and the
-// argument blocks shared by the neighbour kernels (neigh.hip) and the C-ABI host code (udpdk_gpu.hip).
+// argument blocks shared by the neighbour kernels (neigh.hip) and the C-ABI host code (udpdk_gpu_ctl.hip).
 // Device-internal.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -78,7 +78,7 @@ struct NeighLearnArgs {
     uint4    *cand;                // [n_blocks x NL_TILE]
     uint32_t *row;                 // [NL_ROW][n_blocks]
     uint32_t *rbase;               // [n_blocks] events before the workgroup
-    unsigned long long *fuse;      // fan-in words (fanin_arrive), zero between launches
+    unsigned long long *fuse;      // fan-in words (fanin_stage.h), zero between launches
     NeighLearnResult *res;
     uint32_t n, n_blocks;
     uint32_t frames_bytes, rsrc_bytes;

@@ -3,9 +3,9 @@
 // datagram of a TX batch, before tx_build (neigh_resolve). The rules are stated in udpdk_gpu.h
 // (udpdk_gpu_neigh_learn, udpdk_gpu_neigh_resolve); the reference has no neighbour cache.
 //
-// Both kernels have arp_reply's shape: a sweep by every workgroup that only reads the table, and a
-// finish by the launch's last workgroup to arrive (fanin_arrive), which is the table's one writer. No
-// workgroup waits for another. What the sweep cannot decide alone (an ARP sender that may be learned,
+// Both kernels have the shape of fanin_stage.h: a sweep by every workgroup that only reads the table,
+// and a finish by the launch's last workgroup to arrive, which is the table's one writer. What the
+// sweep cannot decide alone (an ARP sender that may be learned,
 // a datagram whose next hop has no usable entry) it compacts in order into cand[]; the finisher takes
 // those in order, one chunk of a workgroup's width at a time with a barrier between chunks, so the
 // table after the call and every count are those of a serial walk. Within a chunk the lanes of one
@@ -29,23 +29,11 @@
 #include "rx_common.h"
 #include "neigh.h"
 #include "wave.h"
+#include "fanin_stage.h"
 
 namespace udpdk {
 
 namespace {
-
-constexpr uint32_t OOR = 0x80000000u;      // a buffer offset out of every range: no memory access, zeros
-
-// Table words as the finisher reads and writes them: agent scope, past the CU's L1 (a later chunk
-// reads what other lanes of the workgroup wrote).
-__device__ __forceinline__ uint32_t tab_ld(const uint32_t *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void tab_st(uint32_t *p, uint32_t v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // The slot of key ip, or NEIGH_NONE: linear probing from the key's home slot to the first empty key,
 // over the whole table at most. COH: agent-scope loads (the finisher); else plain loads (the sweeps,
@@ -55,7 +43,7 @@ __device__ __forceinline__ uint32_t neigh_find(const uint32_t *tab, uint32_t mas
 {
     uint32_t s = neigh_home(ip, shift);
     for (uint32_t k = 0; k <= mask; ++k, s = (s + 1u) & mask) {
-        const uint32_t key = COH ? tab_ld(tab + 4u * s) : tab[4u * s];
+        const uint32_t key = COH ? agent_ld(tab + 4u * s) : tab[4u * s];
         if (key == ip) return s;
         if (key == 0u) return NEIGH_NONE;
     }
@@ -68,7 +56,7 @@ __device__ __forceinline__ uint32_t neigh_claim(uint32_t *tab, uint32_t mask, ui
 {
     uint32_t s = neigh_home(ip, shift);
     for (uint32_t k = 0; k <= mask; ++k, s = (s + 1u) & mask) {
-        uint32_t key = tab_ld(tab + 4u * s);
+        uint32_t key = agent_ld(tab + 4u * s);
         if (key == 0u) {
             key = atomicCAS(tab + 4u * s, 0u, ip);
             if (key == 0u) return s;
@@ -76,95 +64,6 @@ __device__ __forceinline__ uint32_t neigh_claim(uint32_t *tab, uint32_t mask, ui
         if (key == ip) return s;
     }
     return NEIGH_NONE;
-}
-
-// The last workgroup g of [0, nb) with rbase[g] <= r (those after it with the same base are empty).
-__device__ __forceinline__ uint32_t block_of(const uint32_t *rbase, uint32_t nb, uint32_t r, uint32_t *first)
-{
-    uint32_t lo = 0u, hi = nb, f = 0u;
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        const uint32_t v = tab_ld(rbase + mid);
-        if (v <= r) { lo = mid; f = v; } else hi = mid;
-    }
-    *first = f;
-    return lo;
-}
-
-// Finisher, all BLOCK lanes: the sums of the F row fields over the nb workgroups into tot[] (LDS).
-template <int BLOCK, uint32_t F>
-__device__ __forceinline__ void row_sums(const uint32_t *row, uint32_t nb, uint32_t (*red)[F], uint32_t *tot)
-{
-    const uint32_t tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
-    uint32_t acc[F];
-#pragma unroll
-    for (uint32_t f = 0; f < F; ++f) acc[f] = 0u;
-    for (uint32_t t = tid; t < nb; t += BLOCK) {
-#pragma unroll
-        for (uint32_t f = 0; f < F; ++f) acc[f] += row[(size_t)f * nb + t];
-    }
-#pragma unroll
-    for (uint32_t f = 0; f < F; ++f) {
-        const uint32_t s = wave_sum(acc[f]);
-        if (lane == 0) red[w][f] = s;
-    }
-    __syncthreads();
-    if (tid < F) {
-        uint32_t t = 0u;
-#pragma unroll
-        for (int j = 0; j < BLOCK / 64; ++j) t += red[j][tid];
-        tot[tid] = t;
-    }
-    __syncthreads();
-}
-
-// Finisher, all BLOCK lanes: rbase[g] = the sum of cnt[0 .. g) (a contiguous run of rows per lane),
-// written at agent scope and complete when this returns.
-template <int BLOCK>
-__device__ __forceinline__ void row_bases(const uint32_t *cnt, uint32_t *rbase, uint32_t nb, uint32_t *wsum)
-{
-    const uint32_t tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
-    const uint32_t per = (nb + BLOCK - 1u) / BLOCK;
-    const uint32_t b0 = min(nb, tid * per), b1 = min(nb, b0 + per);
-    uint32_t su = 0u;
-    for (uint32_t t = b0; t < b1; ++t) su += cnt[t];
-    uint32_t wt;
-    uint32_t u = wave_excl_scan(su, &wt);
-    if (lane == 0) wsum[w] = wt;
-    __syncthreads();
-    for (uint32_t j = 0; j < w; ++j) u += wsum[j];
-    for (uint32_t t = b0; t < b1; ++t) {
-        tab_st(rbase + t, u);
-        u += cnt[t];
-    }
-    stores_done();
-    __syncthreads();
-}
-
-// How a workgroup's sweep ends (arp_reply's ending): every wave's stores drained, one agent release,
-// the arrival. True in every lane of the launch's last workgroup, after its acquire.
-// RELEASE = false: what the finisher reads of this workgroup was stored written-through (tab_st), so
-// no release is needed: a sweep that also streams megabytes of output the finisher never reads
-// (neigh_resolve) does not have every workgroup ask for their write-back.
-template <bool RELEASE>
-__device__ __forceinline__ bool arrive_last(unsigned long long *fuse, uint32_t b, uint32_t nb, uint32_t *s_last)
-{
-    stores_done();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if constexpr (RELEASE) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            stores_done();
-        }
-        unsigned long long fin;
-        *s_last = fanin_arrive(fuse, b, nb, 0ull, &fin) ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!*s_last) return false;
-    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    stores_done();
-    __syncthreads();
-    return true;
 }
 
 } // namespace
@@ -290,8 +189,8 @@ neigh_learn(NeighLearnArgs a)
         const bool had = slot != NEIGH_NONE;
         uint32_t t_lo = 0u, t_w2 = 0u;
         if (had) {
-            t_lo = tab_ld(a.tab + 4u * slot + 1u);
-            t_w2 = tab_ld(a.tab + 4u * slot + 2u);
+            t_lo = agent_ld(a.tab + 4u * slot + 1u);
+            t_w2 = agent_ld(a.tab + 4u * slot + 2u);
         }
         __syncthreads();
         // this key's events of the chunk: the one before me, whether one follows, and the first that
@@ -332,9 +231,9 @@ neigh_learn(NeighLearnArgs a)
                 out = (fc != NEIGH_NONE && cr) ? NL_O_FULL : NL_O_IGNORED;
             }
             if (wr && !later) {                                     // the key's last event of the chunk
-                tab_st(a.tab + 4u * slot + 1u, mlo);
-                tab_st(a.tab + 4u * slot + 2u, mhi | ((uint32_t)UDPDK_NEIGH_REACHABLE << 16));
-                tab_st(a.tab + 4u * slot + 3u, a.now);
+                agent_st(a.tab + 4u * slot + 1u, mlo);
+                agent_st(a.tab + 4u * slot + 2u, mhi | ((uint32_t)UDPDK_NEIGH_REACHABLE << 16));
+                agent_st(a.tab + 4u * slot + 3u, a.now);
             }
         }
 #pragma unroll
@@ -419,14 +318,14 @@ neigh_resolve(NeighResolveArgs a)
         for (uint32_t j = 0; j < w; ++j) rank += red[j][NR_R_MISS];
         // (written through, like the row: see arrive_last)
         uint32_t *ce = reinterpret_cast<uint32_t *>(a.cand + (size_t)b * NR_TILE + rank);
-        tab_st(ce, i);
-        tab_st(ce + 1, hop);
+        agent_st(ce, i);
+        agent_st(ce + 1, hop);
     }
     if (tid < NR_ROW) {
         uint32_t t = 0u;
 #pragma unroll
         for (int j = 0; j < NW; ++j) t += red[j][tid];
-        tab_st(a.row + (size_t)tid * nb + b, t);
+        agent_st(a.row + (size_t)tid * nb + b, t);
     }
     if (!arrive_last<false>(a.fuse, b, nb, &s_last)) return;
 
@@ -463,8 +362,8 @@ neigh_resolve(NeighResolveArgs a)
         uint32_t slot = valid ? neigh_find<true>(a.tab, a.mask, a.shift, h) : NEIGH_NONE;
         uint32_t t_w2 = 0u, t_w3 = 0u;
         if (slot != NEIGH_NONE) {
-            t_w2 = tab_ld(a.tab + 4u * slot + 2u);
-            t_w3 = tab_ld(a.tab + 4u * slot + 3u);
+            t_w2 = agent_ld(a.tab + 4u * slot + 2u);
+            t_w3 = agent_ld(a.tab + 4u * slot + 3u);
         }
         __syncthreads();
         uint32_t head = tid;
@@ -480,7 +379,7 @@ neigh_resolve(NeighResolveArgs a)
             if (slot != NEIGH_NONE && st == UDPDK_NEIGH_INCOMPLETE) {
                 out = NR_O_INCOMPLETE;
                 ask = a.now - t_w3 >= a.retrans_ms;
-                if (ask) tab_st(a.tab + 4u * slot + 3u, a.now);
+                if (ask) agent_st(a.tab + 4u * slot + 3u, a.now);
             } else {
                 // an expired entry (the MAC stays, for what it is worth), or none yet
                 out = slot != NEIGH_NONE ? NR_O_EXPIRED : NR_O_INSERTED;
@@ -489,8 +388,8 @@ neigh_resolve(NeighResolveArgs a)
                     out = NR_O_TABLE_FULL;
                 } else {
                     ask = true;
-                    tab_st(a.tab + 4u * slot + 2u, (t_w2 & 0xFFFFu) | ((uint32_t)UDPDK_NEIGH_INCOMPLETE << 16));
-                    tab_st(a.tab + 4u * slot + 3u, a.now);
+                    agent_st(a.tab + 4u * slot + 2u, (t_w2 & 0xFFFFu) | ((uint32_t)UDPDK_NEIGH_INCOMPLETE << 16));
+                    agent_st(a.tab + 4u * slot + 3u, a.now);
                 }
             }
             eres[tid] = out;

@@ -16,18 +16,7 @@
 #include <new>
 #include <vector>
 
-#include "udpdk_gpu.h"
-#include "rx_common.h"
-#include "rx_plan.h"
-#include "rx_filter.h"
-#include "rx_balance.h"
-#include "rx_peer.h"
-#include "rx_mcast.h"
-#include "icmp_reply.h"
-#include "icmp_error.h"
-#include "arp_reply.h"
-#include "igmp_reply.h"
-#include "neigh.h"
+#include "gpu_ctx.h"
 #include "rss_host.h"
 
 using namespace udpdk;
@@ -35,239 +24,6 @@ using namespace udpdk;
 namespace {
 
 constexpr int EVENT_SETS = 256;   // timed calls buffered between two timing reads
-
-struct DevResult {
-    unsigned long long counters[UDPDK_N_COUNTERS];
-    uint32_t total;
-    uint32_t pad;
-    // speculative single-lane compaction: word k = max of (call epoch << 32 | ~tile) over the
-    // tiles t = k mod 64 that did not deliver all their frames (rx_classify); the smallest tile
-    // over the 64 words is the call's first such tile (64 words: a batch with many short tiles
-    // does not serialise on one address)
-    unsigned long long nonfull[UDPDK_SPEC_WORDS];
-};
-
-// Per-call kernel timing: start/stop events carried by the kernel dispatches themselves
-// (hipExtLaunchKernelGGL), so timing adds no marker packets between back-to-back kernels.
-constexpr int TIMED_KERNELS = 3;  // classify, scan, scatter (single-lane path: compact)
-struct TimingSet {
-    hipEvent_t ev[2 * TIMED_KERNELS];
-    bool used[TIMED_KERNELS];
-};
-
-// Device (Pinned = false) or pinned host (Pinned = true) memory of `cap` elements that its holder
-// owns: sized by ensure(), freed by release() (or, at the latest, with the holder). Not copyable:
-// the workspaces below are held by value and pointed at (udpdk_gpu_ctx::flt_last and the like).
-int hip_rc(udpdk_gpu_ctx *c, hipError_t e);    // 0, or -EIO with c->last_err set
-
-template <typename T, bool Pinned>
-struct Buf {
-    T *p = nullptr;
-    size_t cap = 0;                            // elements
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf &operator=(const Buf &) = delete;
-    ~Buf() { release(); }
-    operator T *() const { return p; }
-    T *operator->() const { return p; }
-    // Room for `count` elements. Nothing happens while they fit; otherwise the old memory is freed
-    // (which synchronises the device, so only ever on growth) and exactly `count` are allocated,
-    // not zeroed. On failure the buffer is left empty.
-    int ensure(udpdk_gpu_ctx *c, size_t count, unsigned host_flags = hipHostMallocDefault)
-    {
-        if (cap >= count) return 0;
-        T *old = p;
-        p = nullptr;
-        cap = 0;
-        void *q = nullptr;
-        int rc;
-        if (old && (rc = hip_rc(c, Pinned ? hipHostFree(old) : hipFree(old)))) return rc;
-        if ((rc = hip_rc(c, Pinned ? hipHostMalloc(&q, count * sizeof(T), host_flags) : hipMalloc(&q, count * sizeof(T)))))
-            return rc;
-        p = static_cast<T *>(q);
-        cap = count;
-        return 0;
-    }
-    void release()
-    {
-        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        cap = 0;
-    }
-};
-template <typename T> using DevBuf = Buf<T, false>;
-template <typename T> using PinnedBuf = Buf<T, true>;
-
-template <typename... B> void release_all(B &...b) { (b.release(), ...); }
-
-// A stage's device result and its pinned mirror. Two ways to read it: fetch() copies and waits
-// (the context-stream *_stats calls); enqueue_fetch() leaves the copy on the stage's stream, and
-// the mirror is read once that stream was waited for (the pipe forms).
-template <typename R>
-struct ResultSlot {
-    DevBuf<R> dev;
-    PinnedBuf<R> host;
-    bool ran = false;                          // a stage was enqueued (-ENOENT from *_stats until then)
-    int ensure(udpdk_gpu_ctx *c)
-    {
-        const int rc = dev.ensure(c, 1);
-        return rc ? rc : host.ensure(c, 1);
-    }
-    int enqueue_fetch(udpdk_gpu_ctx *c, hipStream_t st)
-    {
-        return hip_rc(c, hipMemcpyAsync(host.p, dev.p, sizeof(R), hipMemcpyDeviceToHost, st));
-    }
-    int fetch(udpdk_gpu_ctx *c, hipStream_t st)
-    {
-        const int rc = enqueue_fetch(c, st);
-        return rc ? rc : hip_rc(c, hipStreamSynchronize(st));
-    }
-    void release() { release_all(dev, host); }
-};
-
-// Workspace of a lane-removal stage (lane_stage: the drop filter, the balance, the peer filter, the
-// membership filter),
-// lazily sized: per stage one per pipe for the sticky mode and one for the explicit calls.
-struct FilterWs {
-    DevBuf<unsigned long long> mask;
-    DevBuf<uint32_t> row, base;
-    DevBuf<uint32_t> pkt, off;                 // sticky mode: the filtered set before it goes back
-                                               // into the caller's buffers
-    ResultSlot<FilterResult> res;
-    hipStream_t stream = nullptr;              // of the last run
-    uint32_t out_cap = 0;
-    void release() { release_all(mask, row, base, pkt, off, res); }
-};
-
-// Workspace of the reuse-port balance stage (rx_balance.hip): the compaction workspace, the
-// frames' choices and the count of balanced frames.
-struct BalanceWs : FilterWs {
-    DevBuf<uint32_t> chosen;
-    DevBuf<uint32_t> cnt;                      // frames balanced
-    PinnedBuf<uint32_t> h_cnt;
-    void release()
-    {
-        FilterWs::release();
-        release_all(chosen, cnt, h_cnt);
-    }
-};
-
-// Workspace of the reply plan (tx_reply.hip), lazily sized; one per context (the context stream).
-struct ReplyWs {
-    DevBuf<uint32_t> row;
-    DevBuf<unsigned long long> base;
-    ResultSlot<ReplyResult> res;
-    void release() { release_all(row, base, res); }
-};
-
-// Workspace of the segment plan (tx_segment.hip), lazily sized; one per context (the context stream).
-struct SegWs {
-    DevBuf<uint32_t> row, send_base;
-    DevBuf<unsigned long long> base;
-    ResultSlot<SegResult> res;
-    void release() { release_all(row, send_base, base, res); }
-};
-
-// Workspace of the ICMP reply stage (icmp_reply.hip), lazily sized by the context's max_frames: one
-// for the context stream (udpdk_gpu_icmp_reply) and one per pipe (udpdk_gpu_pipe_icmp_reply).
-struct IcmpWs {
-    DevBuf<IcmpEntry> cand;
-    DevBuf<uint32_t> row;                      // the rows, then ubase and rbase
-    DevBuf<unsigned long long> bbase;
-    ResultSlot<IcmpResult> res;
-    void release() { release_all(cand, row, bbase, res); }
-};
-
-// The ICMP error stage (icmp_error.hip) keeps only its counters: one slot for the context stream
-// (udpdk_gpu_icmp_errors) and one per pipe (udpdk_gpu_pipe_icmp_errors).
-using IcmpErrWs = ResultSlot<IcmpErrResult>;
-
-// Workspace of the ARP reply stage (arp_reply.hip), lazily sized by the context's max_frames: one for
-// the context stream (udpdk_gpu_arp_reply) and one per pipe (udpdk_gpu_pipe_arp_reply).
-struct ArpWs {
-    DevBuf<ArpEntry> cand;
-    DevBuf<uint32_t> row;                      // the rows, then rbase
-    DevBuf<unsigned long long> fuse;           // fan-in words, zeroed once: every launch leaves zeros
-    ResultSlot<ArpResult> res;
-    void release() { release_all(cand, row, fuse, res); }
-};
-
-// Workspace of the IGMP query responder (igmp_reply.hip), lazily sized by the context's max_frames: one
-// for the context stream (udpdk_gpu_igmp_reply) and one per pipe (udpdk_gpu_pipe_igmp_reply).
-struct IgmpQWs {
-    DevBuf<uint32_t> row;                      // the rows
-    DevBuf<uint32_t> bits;                     // the answer set, zeroed once: every launch leaves zeros
-    DevBuf<unsigned long long> fuse;           // fan-in words, zeroed once: every launch leaves zeros
-    ResultSlot<IgmpQResult> res;
-    void release() { release_all(row, bits, fuse, res); }
-};
-
-// Workspaces of the neighbour stages (neigh.hip), lazily sized: the learn stage has one for the
-// context stream (udpdk_gpu_neigh_learn) and one per pipe (udpdk_gpu_pipe_neigh_learn), the resolve
-// stage one (the context stream).
-template <typename E, typename R>
-struct NeighWs {
-    DevBuf<E> cand;
-    DevBuf<uint32_t> row;                      // the rows, then rbase
-    DevBuf<unsigned long long> fuse;           // fan-in words, zeroed once: every launch leaves zeros
-    ResultSlot<R> res;
-    void release() { release_all(cand, row, fuse, res); }
-};
-using NeighLearnWs = NeighWs<uint4, NeighLearnResult>;
-using NeighResolveWs = NeighWs<uint2, NeighResolveResult>;
-
-// The sticky lane-removal stages, in the order rx_on_pipe applies them.
-enum { ST_DROP, ST_BALANCE, ST_PEER, ST_MCAST, N_STICKY };
-
-// One RX pipe = a stream and the per-call workspace. With pipelining depth d > 1, consecutive
-// udpdk_gpu_rx calls rotate over d pipes, so one batch's prologue, tail and compaction overlap
-// the other batches' streaming phases (the calls are independent: distinct batches and output
-// buffers). Depth 3 is the measured optimum for 1 M x 64 B (tools/probe/classify_probe: classify
-// + compaction 22.2 / 19.0 / 15.5 / 17.4 us per batch at 1 / 2 / 3 / 4 streams; 4 streams exceed
-// the box's 4 hardware queues with the context stream's own traffic).
-struct Pipe {
-    hipStream_t stream = nullptr;
-    DevBuf<uint32_t> hist, partial;
-    DevBuf<uint32_t> base;                    // [tiles][lanes] absolute positions (rx_scan_cols)
-    DevBuf<unsigned long long> agg;           // rx_scan_cols look-back words, one per lane block
-    DevBuf<uint32_t> ticket;                  // rx_scan_cols lane-block tickets
-    uint32_t epoch = 0;                       // rx_scan_cols calls on this pipe (look-back tag)
-    uint32_t spec_epoch = 0;                  // speculative compaction calls (DevResult::nonfull tag)
-    DevBuf<unsigned long long> fuse;          // rx_classify fused-completion fan-in words (zeroed)
-    DevBuf<uint32_t> tile_cnt;
-    ResultSlot<DevResult> res;                // counters, total; the mirror is filled by enqueue_result
-    hipEvent_t tail = nullptr;                // join point for udpdk_gpu_join
-    bool dirty = false;                       // work enqueued since the last join
-    uint32_t last_tiles = 0;                  // tiles of this pipe's last call (counter rows)
-    uint32_t last_lane_cap = 0;
-    FilterWs flt;                             // sticky drop filter
-    BalanceWs bal;                            // sticky reuse-port balance
-    FilterWs peer;                            // sticky peer filter
-    FilterWs mcast;                           // sticky membership filter
-    FilterWs *const sticky[N_STICKY] = {&flt, &bal, &peer, &mcast};
-    bool sticky_ran[N_STICKY] = {};           // this pipe's last call ran the stage
-    const udpdk_rx_stats_t *stats_of = nullptr;   // the stats block read_result filled last, and what each
-    uint32_t removed[N_STICKY] = {};              // stage removed in that call (udpdk_gpu_rx_removed,
-                                                  // udpdk_gpu_rx_peer_removed, udpdk_gpu_rx_mcast_removed)
-    // host-resident batches (udpdk_gpu_rx_host[_async]): staging, lazily sized
-    DevBuf<uint8_t> st_frames_d, st_desc_d, st_out_d;
-    PinnedBuf<uint8_t> st_frames_h, st_desc_h;
-    udpdk_rx_stats_t *host_stats = nullptr;   // outstanding async host call: where its stats go
-    udpdk_rx_batch_t staged{};                // device view of the last host batch staged here
-    const uint32_t *staged_meta = nullptr;    // and its verdict words
-    IcmpWs icmp;                              // udpdk_gpu_pipe_icmp_reply on this pipe's stream
-    IcmpErrWs icmp_err;                       // udpdk_gpu_pipe_icmp_errors on this pipe's stream
-    ArpWs arp;                                // udpdk_gpu_pipe_arp_reply on this pipe's stream
-    IgmpQWs igmp;                             // udpdk_gpu_pipe_igmp_reply on this pipe's stream
-    NeighLearnWs nlearn;                      // udpdk_gpu_pipe_neigh_learn on this pipe's stream
-    void release()
-    {
-        release_all(hist, partial, base, agg, ticket, fuse, tile_cnt, res, flt, bal, peer, mcast, st_frames_d,
-                    st_desc_d, st_out_d, st_frames_h, st_desc_h, icmp, icmp_err, arp, igmp, nlearn);
-    }
-};
-constexpr int MAX_PIPES = 4;
-constexpr size_t FUSE_BYTES = 128u * UDPDK_FUSE_LINES;   // one 128-B line per fan-in / repair word
 constexpr size_t HINT_BYTES = 192u;
 constexpr uint32_t RSS_FUSE_MAX_ENTRIES = 8192u;   // rss_hash's last workgroup scans <= this many
 #ifndef UDPDK_HINT_WINDOW
@@ -277,121 +33,30 @@ constexpr uint32_t RSS_FUSE_MAX_ENTRIES = 8192u;   // rss_hash's last workgroup 
 
 } // namespace
 
-struct udpdk_gpu_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;             // = pipes[0].stream: the context stream
-    int last_err = 0;
-    uint32_t max_frames = 0, max_lanes = 0;
+// gpu_ctx.h's helpers
+namespace udpdk {
 
-    // bind snapshot (device)
-    DevBuf<uint4> port_tab;             // [65536]
-    DevBuf<uint2> binds;
-    DevBuf<uint4> slots;
-    uint32_t n_slots = 0;
-    uint32_t n_lanes = 1, lane_mask = 0xFFFFFFFFu, key_bits = 0, max_fanout = 0;
-    // the bound ports when there are at most UDPDK_INLINE_PORTS (RxArgs::inl)
-    uint32_t inl = 0, n_inl = 0, inl_port[UDPDK_INLINE_PORTS] = {};
-    uint4 inl_ent[UDPDK_INLINE_PORTS] = {};
-    RxKnobs knobs;                 // the environment knobs, parsed once at creation (rx_plan.h)
-    // Kernel hints (pinned host memory the kernels write, RxArgs::hint): the call sequence number
-    // of the last call that ran a tail pass / had a tile before the last not full. The single-lane
-    // path takes rx_classify<1> and the fused completion while neither was seen in the last
-    // UDPDK_HINT_WINDOW calls; both forms are exact for any batch, the hint only picks the faster.
-    PinnedBuf<uint32_t> hint;
-    uint32_t rx_seq = 0;
-    bool have_snapshot = false;
-
-    // RX workspace, one set per pipe
-    Pipe pipes[MAX_PIPES];
-    int depth = 1;                            // udpdk_gpu_pipeline_depth
-    uint64_t rx_calls = 0;
-    int last_pipe = -1;                       // pipe of the last udpdk_gpu_rx (-1: none yet)
-    RxCaps caps{};                            // entries of each pipe's hist / partial / tile_cnt
-
-    uint64_t host_calls = 0;                  // udpdk_gpu_rx_host_async calls (pipe choice)
-
-    uint32_t drop_flags = 0;                  // udpdk_gpu_rx_drop: UDPDK_RX_DROP_* (0: no stage)
-    FilterWs xflt;                            // explicit udpdk_gpu_rx_filter calls
-    FilterWs *flt_last = nullptr;             // the last filter run (udpdk_gpu_rx_drop_stats)
-    bool bal_on = false;                      // udpdk_gpu_rx_balance: the sticky balance stage
-    DevBuf<uint8_t> bal_rp;                   // [max_lanes] its lane flags (zero past what was given)
-    DevBuf<uint32_t> bal_ktab;                // key windows of the default RSS configuration (no
-                                              // udpdk_gpu_rss_config on this context)
-    BalanceWs xbal;                           // explicit udpdk_gpu_rx_balance_select calls
-    BalanceWs *bal_last = nullptr;            // the last balance run (udpdk_gpu_rx_balance_stats)
-    bool peer_on = false;                     // udpdk_gpu_rx_peer: the sticky peer filter
-    DevBuf<uint2> peer_tab;                   // [max_lanes] its records (off past what was given)
-    FilterWs xpeer;                           // explicit udpdk_gpu_rx_peer_select calls
-    FilterWs *peer_last = nullptr;            // the last peer filter run (udpdk_gpu_rx_peer_stats)
-    bool mcast_on = false;                    // udpdk_gpu_rx_mcast: the sticky membership filter
-    DevBuf<uint8_t> mcast_mc;                 // [max_lanes] its lane flags (zero past what was given)
-    DevBuf<uint2> mcast_tab;                  // its membership table, 1 << mcast_lg slots
-    uint32_t mcast_lg = 0;
-    FilterWs xmcast;                          // explicit udpdk_gpu_rx_mcast_select calls
-    FilterWs *mcast_last = nullptr;           // the last membership filter run (udpdk_gpu_rx_mcast_stats)
-    ReplyWs rpl;                              // udpdk_gpu_tx_reply_plan / udpdk_gpu_tx_reply
-    SegWs seg;                                // udpdk_gpu_tx_segment_plan / udpdk_gpu_tx_segment
-    IcmpWs icmp;                              // udpdk_gpu_icmp_reply (the context stream)
-    IcmpErrWs icmp_err;                       // udpdk_gpu_icmp_errors (the context stream)
-    ArpWs arp;                                // udpdk_gpu_arp_reply (the context stream)
-    IgmpQWs igmp;                             // udpdk_gpu_igmp_reply (the context stream)
-    DevBuf<uint32_t> neigh_tab;               // udpdk_gpu_neigh_create: four dwords per entry
-    uint32_t neigh_entries = 0;               // 0: no table
-    NeighLearnWs nlearn;                      // udpdk_gpu_neigh_learn (the context stream)
-    NeighResolveWs nresolve;                  // udpdk_gpu_neigh_resolve
-
-    unsigned long long *dbg = nullptr;        // diagnostic stamp buffer (UDPDK_STAMPS builds)
-    Reasm *reasm = nullptr;                   // udpdk_gpu_frag_table_create
-    // receive-side scaling (udpdk_gpu_rss_config)
-    bool rss_ready = false;
-    RssArgs rss{};
-    DevBuf<uint16_t> rss_reta;
-    DevBuf<uint32_t> rss_ktab;                // [12][256] key windows
-    DevBuf<uint8_t> rss_qid;
-    DevBuf<uint32_t> rss_hist, rss_partial, rss_total;
-    DevBuf<unsigned long long> rss_fuse;      // rss_hash fan-in words (fused queue bases)
-    bool rss_no_fuse = false;                 // UDPDK_RSS_FUSE=0 (tests, A/B): the rss_base launch
-    bool rss_trace = false;                   // UDPDK_RSS_TRACE (diagnostic): the form of every call on stderr
-
-    // timing
-    uint32_t timing_every = 0;                // 0 off, N: events on every Nth call
-    uint64_t timing_calls = 0;
-    TimingSet *sets = nullptr;
-    int n_sets_used = 0;
-    double ms[UDPDK_N_KERNEL_IDS] = {};
-    uint32_t launches[UDPDK_N_KERNEL_IDS] = {};
-
-    // All the memory above (udpdk_gpu_ctx_destroy; whatever is missing here goes with the context)
-    void release()
-    {
-        for (Pipe &P : pipes) P.release();
-        release_all(port_tab, binds, slots, hint, xflt, bal_rp, bal_ktab, xbal, peer_tab, xpeer, mcast_mc, mcast_tab,
-                    xmcast, rpl, seg, icmp,
-                    icmp_err, arp, igmp, neigh_tab, nlearn, nresolve, rss_reta, rss_ktab, rss_qid, rss_hist, rss_partial, rss_total, rss_fuse);
-    }
-};
-
-#define HIPC(ctx, expr)                                                      \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) {                                              \
-            if (ctx) (ctx)->last_err = (int)e_;                              \
-            return -EIO;                                                     \
-        }                                                                    \
-    } while (0)
-
-namespace {
-
-// Range of the frames buffer resource. Buffer loads are range-checked per dword (a dword is
-// returned only if it ends within the range, zero otherwise, with no memory access:
-// tools/probe/range_probe.hip) and the RX kernels load at byte-aligned frame offsets, so a
-// dword holding the last frame bytes may end up to 3 bytes past frames_bytes: the range is
-// frames_bytes + 3 rounded up to a dword, inside the UDPDK_GPU_FRAMES_TAILROOM bytes the frames
-// buffer must keep readable after frames_bytes (udpdk_gpu.h).
 uint32_t frames_rsrc_bytes(uint64_t frames_bytes)
 {
     return (uint32_t)std::min<uint64_t>((frames_bytes + 3 + 3) & ~3ull, 0xFFFFFFFCull);
 }
+
+int hip_rc(udpdk_gpu_ctx *c, hipError_t e)
+{
+    HIPC(c, e);
+    return 0;
+}
+
+int sync_all(udpdk_gpu_ctx *c)
+{
+    for (Pipe &P : c->pipes)
+        if (P.stream) HIPC(c, hipStreamSynchronize(P.stream));
+    return 0;
+}
+
+} // namespace udpdk
+
+namespace {
 
 int fold_timing(udpdk_gpu_ctx *c)
 {
@@ -478,26 +143,15 @@ int join_pipes(udpdk_gpu_ctx *c)
     return 0;
 }
 
-int sync_all(udpdk_gpu_ctx *c)
-{
-    for (Pipe &P : c->pipes)
-        if (P.stream) HIPC(c, hipStreamSynchronize(P.stream));
-    return 0;
-}
+} // namespace
 
-int hip_rc(udpdk_gpu_ctx *c, hipError_t e)
-{
-    HIPC(c, e);
-    return 0;
-}
-
-// How a call that works on the context stream starts, once its arguments have passed: select the
-// device and, with pipelining on, order the other pipes' work before it.
-int on_ctx_stream(udpdk_gpu_ctx *c)
+int udpdk::on_ctx_stream(udpdk_gpu_ctx *c)
 {
     HIPC(c, hipSetDevice(c->device));
     return c->depth > 1 ? join_pipes(c) : 0;
 }
+
+namespace {
 
 // One lane-removal stage over a lane set on stream st: the stage's mark kernel fills the keep masks
 // and rows, then rx_filter_base and rx_filter_write compact (rx_filter.h). `mark` gets the filled
@@ -569,15 +223,6 @@ int sticky_stage(udpdk_gpu_ctx *c, Pipe &P, int stage, const udpdk_rx_out_t *o, 
     HIPC(c, hipGetLastError());
     P.sticky_ran[stage] = true;
     return 0;
-}
-
-// The context-stream form of a *_stats call: the stage's result into its mirror, waited for.
-template <typename R>
-int ctx_result(udpdk_gpu_ctx *c, ResultSlot<R> &slot)
-{
-    if (!slot.ran) return -ENOENT;
-    HIPC(c, hipSetDevice(c->device));
-    return slot.fetch(c, c->stream);
 }
 
 } // namespace
@@ -2373,849 +2018,6 @@ int udpdk_gpu_tx_segment_stats(udpdk_gpu_ctx *c, udpdk_tx_segment_stats_t *st)
     st->too_long = r->too_long;
     st->bad_range = r->bad_range;
     st->too_many = r->too_many;
-    st->no_room = r->no_room;
-    return st->no_room ? -ENOSPC : 0;
-}
-
-namespace {
-
-// Argument checks of udpdk_gpu_icmp_reply and its pipe form: nothing is enqueued unless all pass.
-int icmp_check(const udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
-               const uint32_t *meta_dev, uint32_t flags, uint32_t mtu, const udpdk_icmp_out_t *o)
-{
-    if (!c || !cfg || !bt || !meta_dev || !o) return -EINVAL;
-    if (!flags || (flags & ~UDPDK_ICMP_ALL)) return -EINVAL;
-    if (mtu && (mtu < 68u || mtu > 65535u || (mtu - 20u) % 8u)) return -EINVAL;
-    if (bt->frames_bytes >= (1ull << 32) || o->out_cap >= (1ull << 32)) return -EINVAL;
-    if (!o->frames_dev || !o->reply_off_dev || !o->origin_dev) return -EINVAL;
-    if ((uintptr_t)o->frames_dev & 15u) return -EINVAL;
-    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
-    if (bt->frames_dev) {
-        // the frame buffer with its tailroom against [frames_dev, frames_dev + out_cap)
-        const uintptr_t f0 = (uintptr_t)bt->frames_dev, f1 = f0 + bt->frames_bytes + UDPDK_GPU_FRAMES_TAILROOM;
-        const uintptr_t o0 = (uintptr_t)o->frames_dev, o1 = o0 + o->out_cap;
-        if (o0 < f1 && f0 < o1) return -EINVAL;
-    }
-    return 0;
-}
-
-// The stage (icmp_reply.hip) on stream st with workspace W: scan, base, build.
-int icmp_enqueue(udpdk_gpu_ctx *c, IcmpWs &W, hipStream_t st, const udpdk_tx_config_t *cfg,
-                 const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, uint32_t flags, uint32_t mtu,
-                 uint32_t err_limit, const udpdk_icmp_out_t *o)
-{
-    const uint32_t nb = ceil_div(bt->n, ICMP_TILE);
-    const size_t rows = std::max<size_t>(ceil_div(std::max(bt->n, c->max_frames), ICMP_TILE), 1);
-    int rc;
-    if ((rc = W.cand.ensure(c, rows * ICMP_TILE)) || (rc = W.row.ensure(c, rows * (ICMP_ROW + 2))) ||
-        (rc = W.bbase.ensure(c, rows)) || (rc = W.res.ensure(c)))
-        return rc;
-    if (!bt->n) {
-        HIPC(c, hipMemsetAsync(o->reply_off_dev, 0, 4, st));
-        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(IcmpResult), st));
-        W.res.ran = true;
-        return 0;
-    }
-    IcmpArgs ia;
-    ia.frames = bt->frames_dev;
-    ia.offset = bt->offset_dev;
-    ia.length = bt->length_dev;
-    ia.meta = meta_dev;
-    ia.out = o->frames_dev;
-    ia.reply_off = o->reply_off_dev;
-    ia.origin = o->origin_dev;
-    ia.cand = W.cand;
-    ia.row = W.row;
-    ia.ubase = W.row + (size_t)ICMP_ROW * nb;
-    ia.rbase = ia.ubase + nb;
-    ia.bbase = W.bbase;
-    ia.res = W.res.dev;
-    ia.n = bt->n;
-    ia.n_blocks = nb;
-    ia.frames_bytes = (uint32_t)bt->frames_bytes;
-    ia.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
-    ia.flags = flags;
-    ia.mtu = mtu;
-    ia.err_limit = err_limit;
-    ia.out_cap = (uint32_t)o->out_cap;
-    ia.max_replies = o->max_replies;
-    ia.src_ip = cfg->src_ip;
-    uint8_t mac[12];
-    memcpy(mac, cfg->dst_mac, 6);   // Ethernet d_addr first, as tx_build
-    memcpy(mac + 6, cfg->src_mac, 6);
-    memcpy(ia.mac_lo, mac, 12);
-    hipLaunchKernelGGL(icmp_scan, dim3(nb), dim3(ICMP_BLOCK), 0, st, ia);
-    HIPC(c, hipGetLastError());
-    hipLaunchKernelGGL(icmp_base, dim3(1), dim3(ICMP_BASE_BLOCK), 0, st, ia);
-    HIPC(c, hipGetLastError());
-    hipLaunchKernelGGL(icmp_build, dim3(nb), dim3(ICMP_BLOCK), 0, st, ia);
-    HIPC(c, hipGetLastError());
-    W.res.ran = true;
-    return 0;
-}
-
-int icmp_stats_out(const IcmpResult *r, udpdk_icmp_stats_t *st)
-{
-    st->bytes_needed = r->bytes_needed;
-    st->echo_replied = r->echo_replied;
-    st->unreach_sent = r->unreach_sent;
-    st->replies = r->echo_replied + r->unreach_sent;
-    st->echo_bad = r->echo_bad;
-    st->limited = r->limited;
-    st->no_room = r->no_room;
-    st->bad_frame = r->bad_frame;
-    return st->no_room ? -ENOSPC : 0;
-}
-
-} // namespace
-
-int udpdk_gpu_icmp_geometry(uint32_t n, uint32_t *frames_per_block, uint32_t *n_blocks)
-{
-    if (!frames_per_block || !n_blocks) return -EINVAL;
-    *frames_per_block = ICMP_TILE;
-    *n_blocks = std::max<uint32_t>(1u, ceil_div(n, ICMP_TILE));
-    return 0;
-}
-
-int udpdk_gpu_icmp_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
-                         const uint32_t *meta_dev, uint32_t flags, uint32_t mtu, uint32_t err_limit,
-                         const udpdk_icmp_out_t *o)
-{
-    int rc = icmp_check(c, cfg, bt, meta_dev, flags, mtu, o);
-    if (rc) return rc;
-    if ((rc = on_ctx_stream(c))) return rc;
-    return icmp_enqueue(c, c->icmp, c->stream, cfg, bt, meta_dev, flags, mtu, err_limit, o);
-}
-
-int udpdk_gpu_icmp_stats(udpdk_gpu_ctx *c, udpdk_icmp_stats_t *st)
-{
-    if (!c || !st) return -EINVAL;
-    const int rc = ctx_result(c, c->icmp.res);
-    return rc ? rc : icmp_stats_out(c->icmp.res.host, st);
-}
-
-int udpdk_gpu_pipe_icmp_reply(udpdk_gpu_ctx *c, int pipe, const udpdk_tx_config_t *cfg,
-                              const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, uint32_t flags,
-                              uint32_t mtu, uint32_t err_limit, const udpdk_icmp_out_t *o)
-{
-    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    int rc = icmp_check(c, cfg, bt, meta_dev, flags, mtu, o);
-    if (rc) return rc;
-    HIPC(c, hipSetDevice(c->device));
-    Pipe &P = c->pipes[pipe];
-    P.dirty = true;
-    if ((rc = icmp_enqueue(c, P.icmp, P.stream, cfg, bt, meta_dev, flags, mtu, err_limit, o))) return rc;
-    // the counts follow on the pipe's stream: udpdk_gpu_pipe_icmp_stats reads them after udpdk_gpu_pipe_wait
-    return P.icmp.res.enqueue_fetch(c, P.stream);
-}
-
-int udpdk_gpu_pipe_icmp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_icmp_stats_t *st)
-{
-    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    const ResultSlot<IcmpResult> &R = c->pipes[pipe].icmp.res;
-    return R.ran ? icmp_stats_out(R.host, st) : -ENOENT;
-}
-
-namespace {
-
-// Argument checks of udpdk_gpu_icmp_errors and its pipe form: nothing is enqueued unless all pass.
-int icmp_err_check(const udpdk_gpu_ctx *c, const udpdk_rx_batch_t *bt, const uint32_t *meta_dev,
-                   const udpdk_peer_t *peer_dev, uint32_t n_lanes, const uint64_t *err_dev)
-{
-    if (!c || !bt || !meta_dev || !err_dev) return -EINVAL;
-    if (((uintptr_t)peer_dev & 7u) != 0 || ((uintptr_t)err_dev & 7u) != 0) return -EINVAL;
-    if (n_lanes == 0 || n_lanes > UDPDK_GPU_MAX_LANES) return -EINVAL;
-    if (bt->frames_bytes >= (1ull << 32)) return -EINVAL;
-    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
-    if (!c->have_snapshot || c->lane_mask != 0xFFFFFFFFu) return -EINVAL;   // compat mode: a lane is not a sockfd
-    if (!peer_dev && !c->peer_on) return -ENOENT;                          // no sticky table in force
-    return 0;
-}
-
-// The stage (icmp_error.hip) on stream st with workspace W: clear, scan.
-int icmp_err_enqueue(udpdk_gpu_ctx *c, IcmpErrWs &W, hipStream_t st, uint32_t our_ip, const udpdk_rx_batch_t *bt,
-                     const uint32_t *meta_dev, const udpdk_peer_t *peer_dev, uint32_t n_lanes, uint64_t *err_dev)
-{
-    int rc;
-    if ((rc = W.ensure(c))) return rc;
-    unsigned long long *err = reinterpret_cast<unsigned long long *>(err_dev);
-    hipLaunchKernelGGL(icmp_err_clear, dim3(ceil_div(std::max(n_lanes, ICMP_ERR_ROW + 1u), (uint32_t)ICMP_ERR_BLOCK)),
-                       dim3(ICMP_ERR_BLOCK), 0, st, err, n_lanes, W.dev.p);
-    HIPC(c, hipGetLastError());
-    W.ran = true;
-    if (!bt->n) return 0;
-    IcmpErrArgs ea;
-    ea.frames = bt->frames_dev;
-    ea.offset = bt->offset_dev;
-    ea.length = bt->length_dev;
-    ea.meta = meta_dev;
-    ea.port_tab = c->port_tab;
-    ea.binds = c->binds;
-    // the sticky table holds max_lanes records, off past what udpdk_gpu_rx_peer was given
-    ea.peer = peer_dev ? reinterpret_cast<const uint2 *>(peer_dev) : c->peer_tab;
-    ea.err = err;
-    ea.res = W.dev;
-    ea.n = bt->n;
-    ea.frames_bytes = (uint32_t)bt->frames_bytes;
-    ea.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
-    ea.our_ip = our_ip;
-    ea.n_lanes = n_lanes;
-    ea.peer_n = peer_dev ? n_lanes : c->max_lanes;
-    hipLaunchKernelGGL(icmp_err_scan, dim3(ceil_div(bt->n, ICMP_ERR_TILE)), dim3(ICMP_ERR_BLOCK), 0, st, ea);
-    HIPC(c, hipGetLastError());
-    return 0;
-}
-
-void icmp_err_stats_out(const IcmpErrResult *r, udpdk_icmp_err_stats_t *st)
-{
-    st->errors = r->c[ICMP_X_ERRORS];
-    st->msg_bad = r->c[ICMP_X_MSG_BAD];
-    st->quote_bad = r->c[ICMP_X_QUOTE_BAD];
-    st->soft = r->c[ICMP_X_SOFT];
-    st->no_socket = r->c[ICMP_X_NO_SOCKET];
-    st->reported = r->c[ICMP_X_REPORTED];
-    st->bad_frame = r->c[ICMP_X_BAD_FRAME];
-}
-
-} // namespace
-
-int udpdk_gpu_icmp_errors(udpdk_gpu_ctx *c, uint32_t our_ip, const udpdk_rx_batch_t *bt, const uint32_t *meta_dev,
-                          const udpdk_peer_t *peer_dev, uint32_t n_lanes, uint64_t *err_dev)
-{
-    int rc = icmp_err_check(c, bt, meta_dev, peer_dev, n_lanes, err_dev);
-    if (rc) return rc;
-    if ((rc = on_ctx_stream(c))) return rc;
-    return icmp_err_enqueue(c, c->icmp_err, c->stream, our_ip, bt, meta_dev, peer_dev, n_lanes, err_dev);
-}
-
-int udpdk_gpu_icmp_err_stats(udpdk_gpu_ctx *c, udpdk_icmp_err_stats_t *st)
-{
-    if (!c || !st) return -EINVAL;
-    const int rc = ctx_result(c, c->icmp_err);
-    if (!rc) icmp_err_stats_out(c->icmp_err.host, st);
-    return rc;
-}
-
-int udpdk_gpu_pipe_icmp_errors(udpdk_gpu_ctx *c, int pipe, uint32_t our_ip, const udpdk_rx_batch_t *bt,
-                               const uint32_t *meta_dev, const udpdk_peer_t *peer_dev, uint32_t n_lanes,
-                               uint64_t *err_dev)
-{
-    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    int rc = icmp_err_check(c, bt, meta_dev, peer_dev, n_lanes, err_dev);
-    if (rc) return rc;
-    HIPC(c, hipSetDevice(c->device));
-    Pipe &P = c->pipes[pipe];
-    P.dirty = true;
-    if ((rc = icmp_err_enqueue(c, P.icmp_err, P.stream, our_ip, bt, meta_dev, peer_dev, n_lanes, err_dev))) return rc;
-    // the counts follow on the pipe's stream: udpdk_gpu_pipe_icmp_err_stats reads them after udpdk_gpu_pipe_wait
-    return P.icmp_err.enqueue_fetch(c, P.stream);
-}
-
-int udpdk_gpu_pipe_icmp_err_stats(udpdk_gpu_ctx *c, int pipe, udpdk_icmp_err_stats_t *st)
-{
-    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    const IcmpErrWs &W = c->pipes[pipe].icmp_err;
-    if (!W.ran) return -ENOENT;
-    icmp_err_stats_out(W.host, st);
-    return 0;
-}
-
-int udpdk_gpu_icmp_errno(uint32_t code, int *hard)
-{
-    // Linux's icmp_err_convert (net/ipv4/icmp.c): errno and whether the error is fatal
-    static const int err[16] = {ENETUNREACH, EHOSTUNREACH, ENOPROTOOPT, ECONNREFUSED, EMSGSIZE, EOPNOTSUPP,
-                                ENETUNREACH, EHOSTDOWN, ENONET, ENETUNREACH, EHOSTUNREACH, ENETUNREACH,
-                                EHOSTUNREACH, EHOSTUNREACH, EHOSTUNREACH, EHOSTUNREACH};
-    if (hard) *hard = code < 16u ? (int)((ICMP_ERR_HARD_MASK >> code) & 1u) : 0;
-    return code < 16u ? err[code] : 0;
-}
-
-namespace {
-
-// Argument checks of udpdk_gpu_arp_reply and its pipe form: nothing is enqueued unless all pass.
-int arp_check(const udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
-              const uint32_t *meta_dev, const udpdk_arp_out_t *o)
-{
-    if (!c || !cfg || !bt || !meta_dev || !o) return -EINVAL;
-    if (cfg->src_ip == 0u) return -EINVAL;
-    if (bt->frames_bytes >= (1ull << 32)) return -EINVAL;
-    if (!o->frames_dev || !o->origin_dev) return -EINVAL;
-    if ((uintptr_t)o->frames_dev & 15u) return -EINVAL;
-    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
-    if (bt->frames_dev) {
-        // the frame buffer with its tailroom against the slots and the origin entries
-        const uintptr_t f0 = (uintptr_t)bt->frames_dev, f1 = f0 + bt->frames_bytes + UDPDK_GPU_FRAMES_TAILROOM;
-        const uintptr_t o0 = (uintptr_t)o->frames_dev, o1 = o0 + (uint64_t)o->max_replies * ARP_SLOT;
-        const uintptr_t g0 = (uintptr_t)o->origin_dev, g1 = g0 + (uint64_t)o->max_replies * 4u;
-        if ((o0 < f1 && f0 < o1) || (g0 < f1 && f0 < g1)) return -EINVAL;
-    }
-    return 0;
-}
-
-// The stage (arp_reply.hip) on stream st with workspace W: one launch.
-int arp_enqueue(udpdk_gpu_ctx *c, ArpWs &W, hipStream_t st, const udpdk_tx_config_t *cfg,
-                const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, const udpdk_arp_out_t *o)
-{
-    const uint32_t nb = ceil_div(bt->n, ARP_TILE);
-    const size_t rows = std::max<size_t>(ceil_div(std::max(bt->n, c->max_frames), ARP_TILE), 1);
-    int rc;
-    if ((rc = W.cand.ensure(c, rows * ARP_TILE)) || (rc = W.row.ensure(c, rows * (ARP_ROW + 1))) ||
-        (rc = W.res.ensure(c)))
-        return rc;
-    if (!W.fuse) {
-        if ((rc = W.fuse.ensure(c, FUSE_BYTES / 8))) return rc;
-        HIPC(c, hipMemsetAsync(W.fuse, 0, FUSE_BYTES, st));
-    }
-    if (!bt->n) {
-        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(ArpResult), st));
-        W.res.ran = true;
-        return 0;
-    }
-    ArpArgs aa;
-    aa.frames = bt->frames_dev;
-    aa.offset = bt->offset_dev;
-    aa.length = bt->length_dev;
-    aa.meta = meta_dev;
-    aa.out = o->frames_dev;
-    aa.origin = o->origin_dev;
-    aa.cand = W.cand;
-    aa.row = W.row;
-    aa.rbase = W.row + (size_t)ARP_ROW * nb;
-    aa.fuse = W.fuse;
-    aa.res = W.res.dev;
-    aa.n = bt->n;
-    aa.n_blocks = nb;
-    aa.frames_bytes = (uint32_t)bt->frames_bytes;
-    aa.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
-    aa.max_replies = o->max_replies;
-    aa.src_ip = cfg->src_ip;
-    aa.mac_lo = aa.mac_hi = 0u;
-    memcpy(&aa.mac_lo, cfg->src_mac, 4);
-    memcpy(&aa.mac_hi, cfg->src_mac + 4, 2);
-    hipLaunchKernelGGL(arp_reply, dim3(nb), dim3(ARP_BLOCK), 0, st, aa);
-    HIPC(c, hipGetLastError());
-    W.res.ran = true;
-    return 0;
-}
-
-int arp_stats_out(const ArpResult *r, udpdk_arp_stats_t *st)
-{
-    st->arp = r->c[ARP_R_ARP];
-    st->malformed = r->c[ARP_R_MALFORMED];
-    st->other_op = r->c[ARP_R_OTHER_OP];
-    st->own = r->c[ARP_R_OWN];
-    st->sender_bad = r->c[ARP_R_SENDER_BAD];
-    st->not_ours = r->c[ARP_R_NOT_OURS];
-    st->conflict = r->c[ARP_R_CONFLICT];
-    st->eligible = r->c[ARP_R_ELIGIBLE];
-    st->replies = r->replies;
-    st->no_room = r->no_room;
-    st->bad_frame = r->c[ARP_R_BAD_FRAME];
-    return st->no_room ? -ENOSPC : 0;
-}
-
-} // namespace
-
-int udpdk_gpu_arp_geometry(uint32_t n, uint32_t *frames_per_block, uint32_t *n_blocks)
-{
-    if (!frames_per_block || !n_blocks) return -EINVAL;
-    *frames_per_block = ARP_TILE;
-    *n_blocks = std::max<uint32_t>(1u, ceil_div(n, ARP_TILE));
-    return 0;
-}
-
-int udpdk_gpu_arp_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
-                        const uint32_t *meta_dev, const udpdk_arp_out_t *o)
-{
-    int rc = arp_check(c, cfg, bt, meta_dev, o);
-    if (rc) return rc;
-    if ((rc = on_ctx_stream(c))) return rc;
-    return arp_enqueue(c, c->arp, c->stream, cfg, bt, meta_dev, o);
-}
-
-int udpdk_gpu_arp_stats(udpdk_gpu_ctx *c, udpdk_arp_stats_t *st)
-{
-    if (!c || !st) return -EINVAL;
-    const int rc = ctx_result(c, c->arp.res);
-    return rc ? rc : arp_stats_out(c->arp.res.host, st);
-}
-
-int udpdk_gpu_pipe_arp_reply(udpdk_gpu_ctx *c, int pipe, const udpdk_tx_config_t *cfg,
-                             const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, const udpdk_arp_out_t *o)
-{
-    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    int rc = arp_check(c, cfg, bt, meta_dev, o);
-    if (rc) return rc;
-    HIPC(c, hipSetDevice(c->device));
-    Pipe &P = c->pipes[pipe];
-    P.dirty = true;
-    if ((rc = arp_enqueue(c, P.arp, P.stream, cfg, bt, meta_dev, o))) return rc;
-    // the counts follow on the pipe's stream: udpdk_gpu_pipe_arp_stats reads them after udpdk_gpu_pipe_wait
-    return P.arp.res.enqueue_fetch(c, P.stream);
-}
-
-int udpdk_gpu_pipe_arp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_arp_stats_t *st)
-{
-    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    const ResultSlot<ArpResult> &R = c->pipes[pipe].arp.res;
-    return R.ran ? arp_stats_out(R.host, st) : -ENOENT;
-}
-
-namespace {
-
-// Argument checks of udpdk_gpu_igmp_reply and its pipe form: nothing is enqueued unless all pass.
-int igmp_check(const udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
-               const uint32_t *meta_dev, const uint32_t *groups_dev, uint32_t n_groups, const udpdk_igmp_out_t *o)
-{
-    if (!c || !cfg || !bt || !meta_dev || !o) return -EINVAL;
-    if (cfg->src_ip == 0u || n_groups > IGMP_MAX_GROUPS || (!groups_dev && n_groups)) return -EINVAL;
-    if (bt->frames_bytes >= (1ull << 32)) return -EINVAL;
-    if (!o->frames_dev || !o->group_index_dev) return -EINVAL;
-    if ((uintptr_t)o->frames_dev & 15u) return -EINVAL;
-    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
-    if (bt->frames_dev) {
-        // the frame buffer with its tailroom against the slots and the index entries
-        const uintptr_t f0 = (uintptr_t)bt->frames_dev, f1 = f0 + bt->frames_bytes + UDPDK_GPU_FRAMES_TAILROOM;
-        const uintptr_t o0 = (uintptr_t)o->frames_dev, o1 = o0 + (uint64_t)o->max_reports * IGMP_SLOT;
-        const uintptr_t g0 = (uintptr_t)o->group_index_dev, g1 = g0 + (uint64_t)o->max_reports * 4u;
-        if ((o0 < f1 && f0 < o1) || (g0 < f1 && f0 < g1)) return -EINVAL;
-    }
-    return 0;
-}
-
-// The stage (igmp_reply.hip) on stream st with workspace W: one launch.
-int igmp_enqueue(udpdk_gpu_ctx *c, IgmpQWs &W, hipStream_t st, const udpdk_tx_config_t *cfg,
-                 const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, const uint32_t *groups_dev, uint32_t n_groups,
-                 const udpdk_igmp_out_t *o)
-{
-    const uint32_t nb = ceil_div(bt->n, IGMP_TILE);
-    const size_t rows = std::max<size_t>(ceil_div(std::max(bt->n, c->max_frames), IGMP_TILE), 1);
-    int rc;
-    if ((rc = W.row.ensure(c, rows * IGMP_ROW)) || (rc = W.res.ensure(c))) return rc;
-    if (!W.fuse) {
-        if ((rc = W.fuse.ensure(c, FUSE_BYTES / 8))) return rc;
-        HIPC(c, hipMemsetAsync(W.fuse, 0, FUSE_BYTES, st));
-    }
-    if (!W.bits) {                               // (each on its own: one may fail where the other did not)
-        if ((rc = W.bits.ensure(c, IGMP_WORDS))) return rc;
-        HIPC(c, hipMemsetAsync(W.bits, 0, IGMP_WORDS * sizeof(uint32_t), st));
-    }
-    if (!bt->n) {
-        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(IgmpQResult), st));
-        W.res.ran = true;
-        return 0;
-    }
-    IgmpQArgs ga;
-    ga.frames = bt->frames_dev;
-    ga.offset = bt->offset_dev;
-    ga.length = bt->length_dev;
-    ga.meta = meta_dev;
-    ga.groups = groups_dev;
-    ga.out = o->frames_dev;
-    ga.group_index = o->group_index_dev;
-    ga.row = W.row;
-    ga.bits = W.bits;
-    ga.fuse = W.fuse;
-    ga.res = W.res.dev;
-    ga.n = bt->n;
-    ga.n_blocks = nb;
-    ga.frames_bytes = (uint32_t)bt->frames_bytes;
-    ga.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
-    ga.n_groups = n_groups;
-    ga.max_reports = o->max_reports;
-    ga.src_ip = cfg->src_ip;
-    ga.mac_lo = ga.mac_hi = 0u;
-    memcpy(&ga.mac_lo, cfg->src_mac, 4);
-    memcpy(&ga.mac_hi, cfg->src_mac + 4, 2);
-    hipLaunchKernelGGL(igmp_reply, dim3(nb), dim3(IGMP_BLOCK), 0, st, ga);
-    HIPC(c, hipGetLastError());
-    W.res.ran = true;
-    return 0;
-}
-
-int igmp_stats_out(const IgmpQResult *r, udpdk_igmp_stats_t *st)
-{
-    st->igmp = r->c[IGMP_R_IGMP];
-    st->malformed = r->c[IGMP_R_MALFORMED];
-    st->bad_cksum = r->c[IGMP_R_BAD_CKSUM];
-    st->other_type = r->c[IGMP_R_OTHER_TYPE];
-    st->bad_dst = r->c[IGMP_R_BAD_DST];
-    st->general = r->c[IGMP_R_GENERAL];
-    st->not_member = r->c[IGMP_R_NOT_MEMBER];
-    st->specific = r->c[IGMP_R_SPECIFIC];
-    st->reports = r->reports;
-    st->no_room = r->no_room;
-    st->bad_frame = r->c[IGMP_R_BAD_FRAME];
-    return st->no_room ? -ENOSPC : 0;
-}
-
-} // namespace
-
-int udpdk_gpu_igmp_geometry(uint32_t n, uint32_t *frames_per_block, uint32_t *n_blocks)
-{
-    if (!frames_per_block || !n_blocks) return -EINVAL;
-    *frames_per_block = IGMP_TILE;
-    *n_blocks = std::max<uint32_t>(1u, ceil_div(n, IGMP_TILE));
-    return 0;
-}
-
-int udpdk_gpu_igmp_reply(udpdk_gpu_ctx *c, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
-                         const uint32_t *meta_dev, const uint32_t *groups_dev, uint32_t n_groups,
-                         const udpdk_igmp_out_t *o)
-{
-    int rc = igmp_check(c, cfg, bt, meta_dev, groups_dev, n_groups, o);
-    if (rc) return rc;
-    if ((rc = on_ctx_stream(c))) return rc;
-    return igmp_enqueue(c, c->igmp, c->stream, cfg, bt, meta_dev, groups_dev, n_groups, o);
-}
-
-int udpdk_gpu_igmp_stats(udpdk_gpu_ctx *c, udpdk_igmp_stats_t *st)
-{
-    if (!c || !st) return -EINVAL;
-    const int rc = ctx_result(c, c->igmp.res);
-    return rc ? rc : igmp_stats_out(c->igmp.res.host, st);
-}
-
-int udpdk_gpu_pipe_igmp_reply(udpdk_gpu_ctx *c, int pipe, const udpdk_tx_config_t *cfg, const udpdk_rx_batch_t *bt,
-                              const uint32_t *meta_dev, const uint32_t *groups_dev, uint32_t n_groups,
-                              const udpdk_igmp_out_t *o)
-{
-    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    int rc = igmp_check(c, cfg, bt, meta_dev, groups_dev, n_groups, o);
-    if (rc) return rc;
-    HIPC(c, hipSetDevice(c->device));
-    Pipe &P = c->pipes[pipe];
-    P.dirty = true;
-    if ((rc = igmp_enqueue(c, P.igmp, P.stream, cfg, bt, meta_dev, groups_dev, n_groups, o))) return rc;
-    // the counts follow on the pipe's stream: udpdk_gpu_pipe_igmp_stats reads them after udpdk_gpu_pipe_wait
-    return P.igmp.res.enqueue_fetch(c, P.stream);
-}
-
-int udpdk_gpu_pipe_igmp_stats(udpdk_gpu_ctx *c, int pipe, udpdk_igmp_stats_t *st)
-{
-    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    const ResultSlot<IgmpQResult> &R = c->pipes[pipe].igmp.res;
-    return R.ran ? igmp_stats_out(R.host, st) : -ENOENT;
-}
-
-namespace {
-
-uint32_t neigh_shift(uint32_t entries) { return 32u - (uint32_t)__builtin_ctz(entries); }
-
-void mac_words(const uint8_t *mac, uint32_t *lo, uint32_t *hi)
-{
-    *lo = *hi = 0u;
-    memcpy(lo, mac, 4);
-    memcpy(hi, mac + 4, 2);
-}
-
-// The table on the host (set, dump, flush): a copy, waited for. All streams are drained first, so
-// no kernel is the table's writer meanwhile.
-int neigh_fetch(udpdk_gpu_ctx *c, std::vector<udpdk_neigh_entry_t> &t)
-{
-    if (!c || !c->neigh_entries) return -EINVAL;
-    HIPC(c, hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    t.resize(c->neigh_entries);
-    HIPC(c, hipMemcpy(t.data(), c->neigh_tab, t.size() * sizeof(t[0]), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int neigh_store(udpdk_gpu_ctx *c, const std::vector<udpdk_neigh_entry_t> &t)
-{
-    HIPC(c, hipMemcpy(c->neigh_tab, t.data(), t.size() * sizeof(t[0]), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// The kernels' probe sequence on the host copy: the slot of e.ip, or the first empty one.
-int neigh_put(std::vector<udpdk_neigh_entry_t> &t, const udpdk_neigh_entry_t &e)
-{
-    const uint32_t mask = (uint32_t)t.size() - 1u;
-    uint32_t s = neigh_home(e.ip, neigh_shift((uint32_t)t.size()));
-    for (uint32_t k = 0; k <= mask; ++k, s = (s + 1u) & mask) {
-        if (t[s].ip != e.ip && t[s].ip != 0u) continue;
-        t[s] = e;
-        t[s].pad = 0;
-        return 0;
-    }
-    return -ENOSPC;
-}
-
-int neigh_cfg_check(const udpdk_gpu_ctx *c, const udpdk_neigh_cfg_t *cfg)
-{
-    if (!c || !cfg || !c->neigh_entries) return -EINVAL;
-    if (cfg->src_ip == 0u || (cfg->flags & ~UDPDK_NEIGH_FALLBACK)) return -EINVAL;
-    return 0;
-}
-
-int neigh_learn_check(const udpdk_gpu_ctx *c, const udpdk_neigh_cfg_t *cfg, const udpdk_rx_batch_t *bt,
-                      const uint32_t *meta_dev)
-{
-    const int rc = neigh_cfg_check(c, cfg);
-    if (rc) return rc;
-    if (!bt || !meta_dev || bt->frames_bytes >= (1ull << 32)) return -EINVAL;
-    if (bt->n && (!bt->frames_dev || !bt->offset_dev || !bt->length_dev)) return -EINVAL;
-    return 0;
-}
-
-// A neighbour workspace for nb workgroups of `tile` units, at least what max_frames needs
-extern "C++" template <typename W>
-int neigh_ws(udpdk_gpu_ctx *c, W &ws, hipStream_t st, uint32_t n, uint32_t tile, uint32_t row_fields)
-{
-    const size_t rows = std::max<size_t>(ceil_div(std::max(n, c->max_frames), tile), 1);
-    int rc;
-    if ((rc = ws.cand.ensure(c, rows * tile)) || (rc = ws.row.ensure(c, rows * (row_fields + 1))) ||
-        (rc = ws.res.ensure(c)))
-        return rc;
-    if (!ws.fuse) {
-        if ((rc = ws.fuse.ensure(c, FUSE_BYTES / 8))) return rc;
-        HIPC(c, hipMemsetAsync(ws.fuse, 0, FUSE_BYTES, st));
-    }
-    return 0;
-}
-
-// The learn stage (neigh.hip) on stream st with workspace W: one launch.
-int neigh_learn_enqueue(udpdk_gpu_ctx *c, NeighLearnWs &W, hipStream_t st, const udpdk_neigh_cfg_t *cfg,
-                        const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, uint32_t now)
-{
-    const uint32_t nb = ceil_div(bt->n, NL_TILE);
-    int rc = neigh_ws(c, W, st, bt->n, NL_TILE, NL_ROW);
-    if (rc) return rc;
-    if (!bt->n) {
-        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(NeighLearnResult), st));
-        W.res.ran = true;
-        return 0;
-    }
-    NeighLearnArgs a;
-    a.frames = bt->frames_dev;
-    a.offset = bt->offset_dev;
-    a.length = bt->length_dev;
-    a.meta = meta_dev;
-    a.tab = c->neigh_tab;
-    a.cand = W.cand;
-    a.row = W.row;
-    a.rbase = W.row + (size_t)NL_ROW * nb;
-    a.fuse = W.fuse;
-    a.res = W.res.dev;
-    a.n = bt->n;
-    a.n_blocks = nb;
-    a.frames_bytes = (uint32_t)bt->frames_bytes;
-    a.rsrc_bytes = frames_rsrc_bytes(bt->frames_bytes);
-    a.mask = c->neigh_entries - 1u;
-    a.shift = neigh_shift(c->neigh_entries);
-    a.src_ip = cfg->src_ip;
-    mac_words(cfg->src_mac, &a.mac_lo, &a.mac_hi);
-    a.now = now;
-    hipLaunchKernelGGL(neigh_learn, dim3(nb), dim3(NL_BLOCK), 0, st, a);
-    HIPC(c, hipGetLastError());
-    W.res.ran = true;
-    return 0;
-}
-
-void neigh_learn_stats_out(const NeighLearnResult *r, udpdk_neigh_learn_stats_t *st)
-{
-    st->arp = r->c[NL_R_ARP];
-    st->malformed = r->c[NL_R_MALFORMED];
-    st->bad_frame = r->c[NL_R_BAD_FRAME];
-    st->other_op = r->c[NL_R_OTHER_OP];
-    st->sender_bad = r->c[NL_R_SENDER_BAD];
-    st->updated = r->o[NL_O_UPDATED];
-    st->refreshed = r->o[NL_O_REFRESHED];
-    st->static_kept = r->o[NL_O_STATIC_KEPT];
-    st->created = r->o[NL_O_CREATED];
-    st->full = r->o[NL_O_FULL];
-    st->ignored = r->o[NL_O_IGNORED];
-}
-
-} // namespace
-
-int udpdk_gpu_neigh_create(udpdk_gpu_ctx *c, uint32_t entries)
-{
-    if (!c || entries < 8u || entries > UDPDK_NEIGH_MAX_ENTRIES || (entries & (entries - 1u))) return -EINVAL;
-    HIPC(c, hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    c->neigh_entries = 0;
-    c->neigh_tab.release();
-    if ((rc = c->neigh_tab.ensure(c, (size_t)entries * 4u))) return rc;
-    HIPC(c, hipMemset(c->neigh_tab, 0, (size_t)entries * 16u));
-    c->neigh_entries = entries;
-    return 0;
-}
-
-int udpdk_gpu_neigh_set(udpdk_gpu_ctx *c, const udpdk_neigh_entry_t *e, uint32_t n)
-{
-    if (!c || (!e && n)) return -EINVAL;
-    for (uint32_t i = 0; i < n; ++i)
-        if (e[i].ip == 0u || (e[i].state != UDPDK_NEIGH_STATIC && e[i].state != UDPDK_NEIGH_REACHABLE)) return -EINVAL;
-    std::vector<udpdk_neigh_entry_t> t;
-    int rc = neigh_fetch(c, t), full = 0;
-    if (rc) return rc;
-    for (uint32_t i = 0; i < n && !full; ++i) full = neigh_put(t, e[i]);
-    rc = neigh_store(c, t);
-    return rc ? rc : full;
-}
-
-int udpdk_gpu_neigh_dump(udpdk_gpu_ctx *c, udpdk_neigh_entry_t *out, uint32_t cap, uint32_t *n)
-{
-    if (!c || !n || (!out && cap)) return -EINVAL;
-    std::vector<udpdk_neigh_entry_t> t;
-    const int rc = neigh_fetch(c, t);
-    if (rc) return rc;
-    uint32_t k = 0;
-    for (const udpdk_neigh_entry_t &e : t) {
-        if (e.ip == 0u) continue;
-        if (k < cap) out[k] = e;
-        ++k;
-    }
-    *n = k;
-    return k > cap ? -ENOSPC : 0;
-}
-
-int udpdk_gpu_neigh_flush(udpdk_gpu_ctx *c, int keep_static)
-{
-    std::vector<udpdk_neigh_entry_t> t;
-    int rc = neigh_fetch(c, t);
-    if (rc) return rc;
-    // (the kept entries are put back by key: a probe sequence ends at the first empty slot)
-    std::vector<udpdk_neigh_entry_t> u(t.size(), udpdk_neigh_entry_t{});
-    if (keep_static)
-        for (const udpdk_neigh_entry_t &e : t)
-            if (e.ip != 0u && e.state == UDPDK_NEIGH_STATIC) (void)neigh_put(u, e);
-    return neigh_store(c, u);
-}
-
-int udpdk_gpu_neigh_geometry(uint32_t *learn_frames_per_block, uint32_t *resolve_per_block)
-{
-    if (!learn_frames_per_block || !resolve_per_block) return -EINVAL;
-    *learn_frames_per_block = NL_TILE;
-    *resolve_per_block = NR_TILE;
-    return 0;
-}
-
-int udpdk_gpu_neigh_class(const udpdk_neigh_cfg_t *cfg, uint32_t dst_ip, uint32_t *next_hop, uint8_t *mac_out)
-{
-    if (!cfg || !next_hop || !mac_out) return -EINVAL;
-    uint32_t s_lo, s_hi, lo, hi;
-    mac_words(cfg->src_mac, &s_lo, &s_hi);
-    const uint32_t cls = neigh_class(cfg->src_ip, cfg->netmask, cfg->gateway, s_lo, s_hi, dst_ip, next_hop, &lo, &hi);
-    memcpy(mac_out, &lo, 4);
-    memcpy(mac_out + 4, &hi, 2);
-    return (int)cls;
-}
-
-int udpdk_gpu_neigh_learn(udpdk_gpu_ctx *c, const udpdk_neigh_cfg_t *cfg, const udpdk_rx_batch_t *bt,
-                          const uint32_t *meta_dev, uint32_t now)
-{
-    int rc = neigh_learn_check(c, cfg, bt, meta_dev);
-    if (rc) return rc;
-    if ((rc = on_ctx_stream(c))) return rc;
-    return neigh_learn_enqueue(c, c->nlearn, c->stream, cfg, bt, meta_dev, now);
-}
-
-int udpdk_gpu_neigh_learn_stats(udpdk_gpu_ctx *c, udpdk_neigh_learn_stats_t *st)
-{
-    if (!c || !st) return -EINVAL;
-    const int rc = ctx_result(c, c->nlearn.res);
-    if (!rc) neigh_learn_stats_out(c->nlearn.res.host, st);
-    return rc;
-}
-
-int udpdk_gpu_pipe_neigh_learn(udpdk_gpu_ctx *c, int pipe, const udpdk_neigh_cfg_t *cfg,
-                               const udpdk_rx_batch_t *bt, const uint32_t *meta_dev, uint32_t now)
-{
-    if (!c || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    int rc = neigh_learn_check(c, cfg, bt, meta_dev);
-    if (rc) return rc;
-    HIPC(c, hipSetDevice(c->device));
-    Pipe &P = c->pipes[pipe];
-    if (!P.stream) return -EINVAL;
-    P.dirty = true;
-    if ((rc = neigh_learn_enqueue(c, P.nlearn, P.stream, cfg, bt, meta_dev, now))) return rc;
-    // the counts follow on the pipe's stream, read after udpdk_gpu_pipe_wait
-    return P.nlearn.res.enqueue_fetch(c, P.stream);
-}
-
-int udpdk_gpu_pipe_neigh_learn_stats(udpdk_gpu_ctx *c, int pipe, udpdk_neigh_learn_stats_t *st)
-{
-    if (!c || !st || pipe < 1 || pipe >= MAX_PIPES) return -EINVAL;
-    const ResultSlot<NeighLearnResult> &R = c->pipes[pipe].nlearn.res;
-    if (!R.ran) return -ENOENT;
-    neigh_learn_stats_out(R.host, st);
-    return 0;
-}
-
-int udpdk_gpu_neigh_resolve(udpdk_gpu_ctx *c, const udpdk_neigh_cfg_t *cfg, const uint32_t *dst_ip_dev,
-                            const int32_t *sockfd_dev, uint32_t n, uint32_t now, const udpdk_neigh_out_t *o)
-{
-    int rc = neigh_cfg_check(c, cfg);
-    if (rc) return rc;
-    if (!dst_ip_dev || !sockfd_dev || !o || !o->dmac_dev || !o->sockfd_out_dev || !o->state_dev) return -EINVAL;
-    if (o->req_cap && (!o->req_dev || !o->req_origin_dev)) return -EINVAL;
-    if (((uintptr_t)o->dmac_dev & 7u) || ((uintptr_t)o->req_dev & 15u)) return -EINVAL;
-    if ((rc = on_ctx_stream(c))) return rc;
-    NeighResolveWs &W = c->nresolve;
-    const uint32_t nb = ceil_div(n, NR_TILE);
-    if ((rc = neigh_ws(c, W, c->stream, n, NR_TILE, NR_ROW))) return rc;
-    if (!n) {
-        HIPC(c, hipMemsetAsync(W.res.dev, 0, sizeof(NeighResolveResult), c->stream));
-        W.res.ran = true;
-        return 0;
-    }
-    NeighResolveArgs a;
-    a.dst_ip = dst_ip_dev;
-    a.sockfd = sockfd_dev;
-    a.dmac = o->dmac_dev;
-    a.sockfd_out = o->sockfd_out_dev;
-    a.state = o->state_dev;
-    a.req = o->req_dev;
-    a.req_origin = o->req_origin_dev;
-    a.tab = c->neigh_tab;
-    a.cand = W.cand;
-    a.row = W.row;
-    a.rbase = W.row + (size_t)NR_ROW * nb;
-    a.fuse = W.fuse;
-    a.res = W.res.dev;
-    a.n = n;
-    a.n_blocks = nb;
-    a.req_cap = o->req_cap;
-    a.mask = c->neigh_entries - 1u;
-    a.shift = neigh_shift(c->neigh_entries);
-    a.src_ip = cfg->src_ip;
-    a.netmask = cfg->netmask;
-    a.gateway = cfg->gateway;
-    mac_words(cfg->src_mac, &a.mac_lo, &a.mac_hi);
-    mac_words(cfg->fallback_mac, &a.fb_lo, &a.fb_hi);
-    a.ttl_ms = cfg->ttl_ms;
-    a.retrans_ms = std::max(cfg->retrans_ms, 1u);
-    a.fallback = (cfg->flags & UDPDK_NEIGH_FALLBACK) ? 1u : 0u;
-    a.now = now;
-    hipLaunchKernelGGL(neigh_resolve, dim3(nb), dim3(NR_BLOCK), 0, c->stream, a);
-    HIPC(c, hipGetLastError());
-    W.res.ran = true;
-    return 0;
-}
-
-int udpdk_gpu_neigh_resolve_stats(udpdk_gpu_ctx *c, udpdk_neigh_resolve_stats_t *st)
-{
-    if (!c || !st) return -EINVAL;
-    const int rc = ctx_result(c, c->nresolve.res);
-    if (rc) return rc;
-    const NeighResolveResult *r = c->nresolve.res.host;
-    st->skipped = r->c[NR_R_SKIPPED];
-    st->bcast = r->c[NR_R_BCAST];
-    st->mcast = r->c[NR_R_MCAST];
-    st->no_route = r->c[NR_R_NO_ROUTE];
-    st->self = r->c[NR_R_SELF];
-    st->hit = r->c[NR_R_HIT];
-    st->expired = r->o[NR_O_EXPIRED];
-    st->incomplete = r->o[NR_O_INCOMPLETE];
-    st->inserted = r->o[NR_O_INSERTED];
-    st->table_full = r->o[NR_O_TABLE_FULL];
-    st->fallback = r->fallback;
-    st->unresolved = r->unresolved;
-    st->requests = r->requests;
     st->no_room = r->no_room;
     return st->no_room ? -ENOSPC : 0;
 }
